@@ -6,7 +6,7 @@ C: num_k = 4 generator updates on the target discrepancy; adapt_trainer.py:155-2
 one synthetic batch of N (source, target) RGB+HHA pairs per GPU.  The timed schedule runs 6 generator forward and 5 generator
 backward passes per step: the reference's literal 7 + 7, minus the two step-B backward passes whose gradients it zeroes unused
 (SURVEY.md section 3.1), minus step B's target forward, which IS step C's first one (solvers/solver.py; bit-identical results).
-The literal 7-forward schedule is measured in the same run and printed next to it (``value_literal_schedule``).
+With ``--full``, the literal 7-forward schedule is measured in the same run and printed next to it (``value_literal_schedule``).
 ``value`` = pairs/s over the whole job, inputs resident in HBM; every step gets a batch it has not seen (a pool of pre-staged
 batches, per-tensor caches dropped), so the per-batch work -- the input's bound and its padded companion -- is inside the timed region.
 
@@ -15,8 +15,18 @@ batches, per-tensor caches dropped), so the per-batch work -- the input's bound 
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  Every kernel family of the step is bracketed by HIP events on the launch stream inside
-the timed region; ``roofline`` prices the kernel with the largest summed time (``dominant``): its algorithmic FLOPs or
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: set-up, ``--warmup`` steps, ``--steps`` timed
+steps, the outputs of the last timed step if ``--dump-outputs DIR`` is given, the line.  Everything below -- per-kernel timing, rooflines,
+the literal schedule, the other configurations, the strict-fp32 arithmetics, the CPU baseline, the collectives -- is measured only with
+``--full`` (the keys stay in the line, as null, without it):
+
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
+
+``--dump-outputs DIR`` writes what the timed path handed its caller after the last timed step (dump_outputs): the two losses and
+the state of G, F1 and F2 as float32 / float64 ``.npy`` files, under 64 MB; the same arguments give the same inputs in every run.
+
+With ``--full``, every kernel family of the step is bracketed by HIP events on the launch stream inside
+the timed region (the last ``--timer_steps``); ``roofline`` prices the kernel with the largest summed time (``dominant``): its algorithmic FLOPs or
 bytes per launch / its average launch duration, against the MFMA peak of the arithmetic it executes or the HBM peak.
 ``roofline_forward`` / ``roofline_wgrad`` are the same for the forward / weight-gradient convolution carrying the most FLOPs.  The pass is matrix-rate bound,
 not HBM bound: ``step_accounting`` says so next to the raw HBM fraction the metric asks for.
@@ -264,7 +274,9 @@ def cpu_baseline(args):
     import torch
     from oracle import ref_loss, ref_mcd, ref_models
     model, phys, logical = host_cpu()
-    threads = max(1, min(phys, logical))
+    # the cores this process may use: its CPU affinity and torch's thread count (OMP_NUM_THREADS) -- not the whole host, which a
+    # process limited to a share of it would oversubscribe
+    threads = max(1, min(phys, logical, len(os.sched_getaffinity(0)), torch.get_num_threads()))
     prev = torch.get_num_threads()
     torch.set_num_threads(threads)
     try:
@@ -298,6 +310,27 @@ def cpu_baseline(args):
             "sample": "CPU oracle, full MCD step (A+B+C, num_k=4; 7 fwd + 7 bwd passes) on %d pair(s) of %dx%dx%d: 1 warm-up + %d timed "
                       "step(s), median %.1f s/step, %d threads on %s (%d physical cores)"
                       % (n, args.input_ch, args.height, args.width, len(times), med, threads, model, phys)}
+
+
+DUMP_MAX_ELEMS = 4 << 20  # float32 elements written per model at most (16 MB): G's 26 M are sampled, F1 / F2 are written whole
+
+
+def dump_outputs(out_dir, c_loss, d_loss, models):
+    """``--dump-outputs DIR``: what the timed path handed its caller after the last timed step -- the two losses ``solver.step``
+    returned (c_loss.npy, d_loss.npy: float64, shape (1,)) and the state it left in G, F1, F2 (g_state.npy, f1_state.npy,
+    f2_state.npy: every floating-point tensor of the model's state_dict -- weights and BatchNorm statistics -- flattened in state_dict
+    order into one float32 vector; a model over DUMP_MAX_ELEMS elements is written at a fixed, seeded, sorted sample of its positions)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "c_loss.npy"), np.array([c_loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "d_loss.npy"), np.array([d_loss], dtype=np.float64))
+    for name, m in zip(("g", "f1", "f2"), models):
+        flat = torch.cat([t.detach().reshape(-1).float() for t in m.state_dict().values() if t.dtype.is_floating_point])
+        if flat.numel() > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            flat = flat[torch.from_numpy(pick).to(flat.device)]
+        np.save(os.path.join(out_dir, name + "_state.npy"), flat.cpu().numpy())
 
 
 def _free_port():
@@ -456,11 +489,21 @@ def _main():
                     help="timed steps of the judged configuration in each strict-fp32 arithmetic (bf16x6, f32 MFMA) after the timed region, "
                          "reported as 'strict_fp32' (0 = skip)")
     ap.add_argument("--timer", choices=sorted(TIMED_FAMILIES), default="all", help="kernel families bracketed by HIP events")
-    ap.add_argument("--timer_steps", type=int, default=1,
+    ap.add_argument("--timer_steps", type=int, default=None,
                     help="how many of the timed steps (the last ones) carry the per-launch HIP events: bracketing all ~1 500 launches "
                          "of a step costs 3.6 %% of its time (measured, profiles/README.md) and such a step runs its weight gradients on "
-                         "the main stream (every pair brackets a kernel running alone), another 3.4 %%; so by default one step pays it")
+                         "the main stream (every pair brackets a kernel running alone), another 3.4 %%; so by default one step pays it "
+                         "with --full, none without")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel timing and rooflines, the literal schedule, one stream, "
+                         "the other MCDSEG_DP_OVERLAP setting, the collectives, other_configs, strict_fp32, step_accounting, cpu_baseline")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write the losses and model state the last timed step produced to DIR/<name>.npy (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.timer_steps is None:
+        args.timer_steps = 1 if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher: become one.  Nothing above or below this line has initialised a GPU in this process.
@@ -510,7 +553,7 @@ def _main():
     mdist.barrier()
     torch.cuda.synchronize()
     ops.WGRAD_STREAM_STATS.update(deferred=0, no_room=0)
-    mdist.COLLECTIVE_EVENTS = [] if mdist.is_distributed() else None
+    mdist.COLLECTIVE_EVENTS = [] if (args.full and mdist.is_distributed()) else None
     t0 = time.perf_counter()
     for i in range(args.steps):
         timer.enabled = i >= args.steps - args.timer_steps
@@ -544,10 +587,12 @@ def _main():
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(el)
     c_loss, d_loss = float(c_loss), float(d_loss)
+    if args.dump_outputs and rank == 0:  # (before anything below steps the solver again)
+        dump_outputs(args.dump_outputs, c_loss, d_loss, models)
 
     # for reference, outside the timed region: the same step with the reference's literal schedule (7 generator forwards)
     literal = None
-    if solver.reuse_tgt and args.literal_steps > 0:
+    if args.full and solver.reuse_tgt and args.literal_steps > 0:
         solver.reuse_tgt = False
         solver.step(*next_batch())
         torch.cuda.synchronize()
@@ -571,7 +616,7 @@ def _main():
     # N > 1, outside the timed region: the same step with the OTHER setting of MCDSEG_DP_OVERLAP (gradients exchanged in buckets during
     # the backward pass instead of one all-reduce of the flat buffer in step(), or the reverse) -- one invocation decides the default
     dp_other = None
-    if mdist.is_distributed() and args.literal_steps > 0:
+    if args.full and mdist.is_distributed() and args.literal_steps > 0:
         from mcdseg import optim as moptim
         was = moptim.DP_OVERLAP
         opts = [o for o in (getattr(solver, "opt_g", None), getattr(solver, "opt_f", None)) if hasattr(o, "_setup_overlap")]
@@ -604,7 +649,7 @@ def _main():
     # likewise outside the timed region: the same step with the weight gradients on the main stream, the same-box
     # price of the second stream
     one_stream = None
-    if ops.OVERLAP_WGRAD != "0" and args.literal_steps > 0:
+    if args.full and ops.OVERLAP_WGRAD != "0" and args.literal_steps > 0:
         mode, ops.OVERLAP_WGRAD = ops.OVERLAP_WGRAD, "0"
         solver.step(*next_batch())
         torch.cuda.synchronize()
@@ -627,7 +672,7 @@ def _main():
 
     others = None
     judged_cfg = (args.net, args.batch, args.height, args.width, args.input_ch) == ("drn_d_38", 16, 480, 640, 6)
-    if world == 1 and not mdist.is_distributed() and judged_cfg and args.other_configs.strip():
+    if args.full and world == 1 and not mdist.is_distributed() and judged_cfg and args.other_configs.strip():
         # free the judged configuration first: cfg5 at N = 32 takes 232 of the 288 GB
         kern_summary = timer.summary()
         reuse_tgt = solver.reuse_tgt
@@ -649,7 +694,7 @@ def _main():
     # the judged configuration in the two STRICT fp32 arithmetics (24-bit operands), after the timed region: what an IEEE-grade
     # product costs next to the default's 22-bit operands
     strict = None
-    if world == 1 and not mdist.is_distributed() and judged_cfg and args.strict_steps > 0 and ops.CONV_MATH == "f16x3":
+    if args.full and world == 1 and not mdist.is_distributed() and judged_cfg and args.strict_steps > 0 and ops.CONV_MATH == "f16x3":
         strict = {}
         for tag, key in (("cfg2_bf16x6", "bf16x6"), ("cfg2_f32", "f32")):
             try:
@@ -694,7 +739,7 @@ def _main():
                 roofline_wg = priced(max(wgk, key=lambda n: wgk[n]["flops"]), wgk)
         # whole-step accounting on the algorithmic work of SURVEY.md 8d (drn_d_38 @ 6x480x640 only)
         step_acc = None
-        if args.net == "drn_d_38" and (args.height, args.width, args.input_ch) == (480, 640, 6):
+        if args.full and args.net == "drn_d_38" and (args.height, args.width, args.input_ch) == (480, 640, 6):
             # passes actually executed per pair: step B's two generator backward passes elided; its target forward is step C's first
             fwd_p, bwd_p = (6 if reuse_tgt else 7), 5
             gf = GF_FWD_PER_IMG * (fwd_p + 2 * bwd_p)
@@ -716,7 +761,7 @@ def _main():
         line = {
             "metric": "RGB-D img/s (6x480x640) MCD train step, drn_d_38", "value": round(value, 3), "unit": "img/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 2),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE_LABEL.get(ops.CONV_MATH, ops.CONV_MATH), "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": DTYPE_LABEL.get(ops.CONV_MATH, ops.CONV_MATH), "data": "synthetic", "full": args.full,
             "config": {"workload": "adapt_trainer MCD early-fusion %s %d-ch, bs=%d/GPU synthetic %dx%d, full A+B+C step (num_k=4)"
                                    % (args.net, args.input_ch, args.batch, args.height, args.width),
                        "pairs_per_gpu": args.batch, "global_pairs": args.batch * world, "parallelism": "dp%d" % world,
@@ -751,7 +796,7 @@ def _main():
                             "tflops": round(v["tflops"], 2), "alg_gbs": round(v["gbs"], 1)}
                         for k, v in sorted(kern.items(), key=lambda kv: -kv[1]["ms"])},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args)
         else:
             line["cpu_baseline"] = None

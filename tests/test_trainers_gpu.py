@@ -382,7 +382,7 @@ def test_bench_with_one_rank_through_rccl(overlap):
     import json
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96", "--no_cpu_baseline",
-            "--literal_steps", "1", "--batch_pool", "1"]
+            "--literal_steps", "1", "--batch_pool", "1", "--full"]
     r = _run_ranks(1, os.path.join(root, "bench.py"), args, extra_env={"MCDSEG_DIST_BACKEND": "nccl", "MCDSEG_DIST_FORCE": "1", "MCDSEG_DP_OVERLAP": overlap,
                                                                       "MCDSEG_DP_BUCKET_MB": "8"})
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -441,7 +441,7 @@ def test_native_rccl_allreduce_one_rank():
     check(L.mcdseg_comm_destroy(comm), "comm_destroy")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     args = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2", "--height", "64", "--width", "96", "--no_cpu_baseline",
-            "--literal_steps", "1", "--batch_pool", "1", "--other_configs", "", "--strict_steps", "0"]
+            "--literal_steps", "1", "--batch_pool", "1", "--other_configs", "", "--strict_steps", "0", "--full"]
     lines = {}
     for native in ("1", "0"):
         r = _run_ranks(1, os.path.join(root, "bench.py"), args, extra_env={"MCDSEG_DIST_BACKEND": "nccl", "MCDSEG_DIST_FORCE": "1",

@@ -8,7 +8,7 @@ timeout 1800 python -m pytest tests/test_model_gpu.py tests/test_kernels_gpu.py 
   > "$OUT/r05b_tests.txt" 2>&1
 tail -25 "$OUT/r05b_tests.txt"
 python tools/probes/winograd_probe.py 2>&1 | grep -v amdgpu.ids | tee "$OUT/r05b_winograd.txt"
-Q="--steps 12 --warmup 4 --no_cpu_baseline --other_configs= --literal_steps 0 --strict_steps 0"
+Q="--full --steps 12 --warmup 4 --no_cpu_baseline --other_configs= --literal_steps 0 --strict_steps 0"
 for i in 1 2; do
   MCDSEG_BN_STATS_ONE=0 python bench.py $Q 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('two-stage stats', d['ms_per_step'], d['kernels'].get('bn_stats_finalize'))"
   python bench.py $Q 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['kernels']; print('one-launch stats', d['ms_per_step'], k.get('bn_stats_finalize')); print({n:(v['launches'],v['avg_ms']) for n,v in k.items() if 'wgrad' in n})"

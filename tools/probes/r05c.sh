@@ -10,7 +10,7 @@ tail -12 "$OUT/r05c_tests.txt"; grep "cfg5 geometry N=" "$OUT/r05c_tests.txt"
 python tools/bench_layers.py --only "L3 64->64" 2>&1 | grep -v amdgpu | tail -3
 MCDSEG_PP_WIDE64=0 python tools/bench_layers.py --only "L3 64->64" 2>&1 | grep -v amdgpu | tail -3
 python tools/bench_layers.py --only "L3 32->64" 2>&1 | grep -v amdgpu | tail -3
-Q="--steps 12 --warmup 4 --no_cpu_baseline --other_configs= --literal_steps 0 --strict_steps 0"
+Q="--full --steps 12 --warmup 4 --no_cpu_baseline --other_configs= --literal_steps 0 --strict_steps 0"
 for i in 1 2; do
   MCDSEG_PP_WIDE64=0 python bench.py $Q 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('4-wave 64-row tiles', d['ms_per_step'])"
   python bench.py $Q 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); k=d['kernels']; print('64 x 640 tile', d['ms_per_step']); print({n:(v['launches'],v['avg_ms'],v['tflops']) for n,v in k.items() if '1, 5, 1, 4' in n or '2, 2, 1, 4' in n})"

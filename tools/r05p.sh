@@ -3,7 +3,7 @@
 # libmcdseg_prev.so (the kernels of commit 0a1c5a8^: before the loss / up-sampler / BatchNorm / tr64 / stem changes)
 cd "$(dirname "$0")/.."
 timeout 900 python -m pytest tests/test_kernels_gpu.py -q -m gpu -x -k "wgrad or stem or conv" 2>&1 | grep -E "passed|failed|Error" | head -5
-B="python bench.py --steps 12 --warmup 4 --no_cpu_baseline --other_configs= --literal_steps 0 --strict_steps 0"
+B="python bench.py --full --steps 12 --warmup 4 --no_cpu_baseline --other_configs= --literal_steps 0 --strict_steps 0"
 for i in 1 2; do
   for lib in prev new; do
     if [ $lib = prev ]; then export MCDSEG_LIB=$PWD/multichannel-semseg-with-uda_amd/mcdseg/libmcdseg_prev.so; else unset MCDSEG_LIB; fi
