@@ -351,6 +351,22 @@ int mcdseg_label_weight_sum(const int64_t* labels, const float* class_weight, in
 size_t mcdseg_predict_workspace_bytes(int32_t N, int32_t HW);
 int mcdseg_predict_labels(const float* z1, const float* z2, uint8_t* labels, float* entropy, int32_t N, int32_t C,
                           int32_t C_used, int32_t HW, void* workspace, size_t workspace_bytes, void* stream);
+/* The same tail fused with the x8 up-sampler that precedes it, so the [N,C,8Hi,8Wi] logits are never stored
+ * (the reference's source_tester.py:119-143: DRNSeg's learned up-sampler; adapt_multitask_tester.py:118-141: the multitask decoder's
+ * bilinear one on pred_semseg1).  z = up8(s, w) as mcdseg_up8_fwd computes it (single input) when w != NULL (w: [C,1,16,16]), else
+ * z = bilinear x8 (align_corners = False) as mcdseg_bilinear8_fwd computes it; then labels [N,8Hi,8Wi] and entropy[0] exactly as
+ * mcdseg_predict_labels(z, NULL, ...) defines them -- the labels equal that composition bit for bit.  C <= 48; one workgroup per image and
+ * band of 8 output rows holds two input rows of the C channels (+ the C kernels) in LDS: 8 C Wi (+ 1024 C) bytes, at most 160 KB. */
+size_t mcdseg_predict_up8_workspace_bytes(int32_t N, int32_t Hi);
+int mcdseg_predict_labels_up8(const float* s, const float* w, uint8_t* labels, float* entropy, int32_t N, int32_t C, int32_t C_used,
+                              int32_t Hi, int32_t Wi, void* workspace, size_t workspace_bytes, void* stream);
+/* Depth image of the multitask tester (adapt_multitask_tester.py:148-155 with transform.py:285-294, unnormalize): d [N,Cd,Hi,Wi] fp32
+ * (Cd = 1 or 3, the depth head) -> img [N,8Hi,8Wi,3] uint8 HWC.  v = bilinear x8 of d (mcdseg_bilinear8_fwd's fp32 values) in channel
+ * Cd == 1 ? 0 : k; t = ((double)v * STD[k] + MEAN[k]) * 255 with every operation rounded in double (numpy's promotion against the
+ * float64 constants MEAN = (.485,.456,.406), STD = (.229,.224,.225)); Cd = 1 broadcasts into three channels as numpy does; the byte
+ * is numpy's np.uint8(t) on x86-64: t truncated to int32, low 8 bits kept, 0 for NaN, +-inf and t outside the int32 range (so
+ * -1.0 -> 255, 300.7 -> 44: an undertrained regressor's values wrap, as in the reference's PNGs).  No workspace. */
+int mcdseg_depth_image_u8(const float* d, uint8_t* img, int32_t N, int32_t Cd, int32_t Hi, int32_t Wi, void* stream);
 /* buf[i] *= *scale (device scalar) -- applies autograd's upstream scalar without a host sync */
 int mcdseg_scale_by_device_scalar(float* buf, const float* scale, int64_t n, void* stream);
 

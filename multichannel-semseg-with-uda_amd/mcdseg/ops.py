@@ -1918,6 +1918,47 @@ def predict_labels(z1, z2=None, n_used=None):
     return labels, ent.reshape(())
 
 
+def _predict_up(s, w, n_used):
+    L = lib()
+    s, w = _req(s, "low-resolution logits"), _req(w, "up8 weight")
+    if s.dim() != 4:
+        raise ValueError("mcdseg: the up-sampling predict tail takes logits [N,C,H,W], got %s" % (tuple(s.shape),))
+    if w is not None:
+        _check_up(s, w)
+    n, c, hi, wi = s.shape
+    n_used = c if n_used is None else int(n_used)
+    labels = torch.empty((n, 8 * hi, 8 * wi), dtype=torch.uint8, device=s.device)
+    ent = torch.empty(1, dtype=torch.float32, device=s.device)
+    ws = _ws(L.mcdseg_predict_up8_workspace_bytes(n, hi), s.device)
+    check(L.mcdseg_predict_labels_up8(_p(s), _p(w), _p(labels), _p(ent), n, c, n_used, hi, wi, _p(ws), ctypes.c_size_t(ws.numel() * 4),
+                                      _stream()), "predict_labels_up8")
+    return labels, ent.reshape(())
+
+
+def predict_labels_up8(s, w, n_used=None):
+    """``predict_labels(up8(s, w), None, n_used)`` without the full-resolution logits: DRNSeg's learned x8 up-sampler and the
+    argmax / entropy tail in one pass (source_tester.py:119-143).  Labels are bitwise those of the two-step composition."""
+    return _predict_up(s, w, n_used)
+
+
+def predict_labels_bilinear8(s, n_used=None):
+    """``predict_labels(bilinear8(s), None, n_used)`` in one pass, for the multitask decoder's pred_semseg1
+    (adapt_multitask_tester.py:118-141)."""
+    return _predict_up(s, None, n_used)
+
+
+def depth_image_u8(d):
+    """bilinear8(d) -> transform.unnormalize -> uint8 HWC image [N,8H,8W,3] (adapt_multitask_tester.py:148-155): numpy's float64
+    arithmetic and np.uint8 cast, bit for bit (values outside [0,255] wrap as they do in the reference).  d: fp32 [N,1 or 3,H,W]."""
+    d = _req(d, "depth prediction")
+    if d.dim() != 4 or d.shape[1] not in (1, 3):
+        raise ValueError("mcdseg: depth_image_u8 takes [N,1,H,W] or [N,3,H,W], got %s" % (tuple(d.shape),))
+    n, cd, hi, wi = d.shape
+    img = torch.empty((n, 8 * hi, 8 * wi, 3), dtype=torch.uint8, device=d.device)
+    check(lib().mcdseg_depth_image_u8(_p(d), _p(img), n, cd, hi, wi, _stream()), "depth_image_u8")
+    return img
+
+
 # ------------------------------------------------------------------------------------------------ MFNet gate fusion
 class _GateMix(torch.autograd.Function):
     @staticmethod
