@@ -497,8 +497,8 @@ static int wgrad_impl(const mcdseg_conv_desc* d, const float* x, const float* dy
 
 // Which kernel mcdseg_conv_wgrad / mcdseg_conv_split_wgrad launch for this geometry (math = 0 for mcdseg_conv_wgrad):
 // 0..3 the f32 plans (128x128, 64x64, 32x32 tiles, tap-packed thin), 10 split arithmetic from fp32 operands, 11 / 12 / 13 / 14 from
-// both pre-split companions: register-transposing, transposed-read 128x128, transposed-read 256x128, transposed-read 64-channel
-// tap pairs, 15 the thin-layer window kernel, 16 transposed-read 128-channel tiles with two taps per workgroup, 17 the eight-wave
+// both pre-split companions: register-transposing (bf16x6), transposed-read 128x128, transposed-read 256x128, transposed-read 64-channel
+// tap pairs, 15 the thin-layer window kernel, 16 retired (two taps per workgroup: measured slower and removed), 17 the eight-wave
 // ping-pong kernel (256 x 256 tiles), 18 its row-of-taps form for the 128-channel layers.  For profilers and the benchmark's per-kernel accounting; never needed to call the operators.
 extern "C" int32_t mcdseg_conv_wgrad_variant(const mcdseg_conv_desc* d, int32_t math, int32_t presplit) {
   if (d == nullptr) return -22;
@@ -509,8 +509,7 @@ extern "C" int32_t mcdseg_conv_wgrad_variant(const mcdseg_conv_desc* d, int32_t 
   if (pl.cfg == 1 && presplit && tr64_applies(d, math, d, d, 1)) return 14;
   if (pl.cfg != 0 || math == 0) return pl.cfg;
   if (!(presplit && (d->Cin & 7) == 0 && (d->Cout & 7) == 0)) return 10;
-  const int v = mcdseg_internal_wgrad_cb_variant(d, math, pl.co_p, pl.ci_p, pl.splits);
-  return v == 3 ? 16 : 11 + v;  // 16: transposed-read 128-row tiles, two taps per workgroup
+  return 11 + mcdseg_internal_wgrad_cb_variant(d, math, pl.co_p, pl.ci_p, pl.splits);
 }
 
 extern "C" int mcdseg_conv_wgrad(const mcdseg_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace,
@@ -529,7 +528,7 @@ extern "C" int mcdseg_conv_split_wgrad(const mcdseg_conv_desc* d, int32_t math, 
 
 // One launch addresses an operand with 32-bit buffer offsets.  The kernels that read the fp32 tensors express padding and ragged
 // channel tails as offsets up to a 128-channel tile past the tensor, which the buffer range check must still reject: (N*C + 128)
-// planes below 2 GiB.  The plans that read both pre-split companions (variants 11..16) mark such accesses with an explicit
+// planes below 2 GiB.  The plans that read both pre-split companions (variants 11..18) mark such accesses with an explicit
 // out-of-range offset and check their own limits (one piece of a companion below 2 GiB): no slack.
 static bool wgrad_reads_companions(const mcdseg_conv_desc* d, int math, bool have_cb) {
   if (!math || !have_cb) return false;

@@ -204,9 +204,10 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_kernel(WgradSplitPara
 // the tile: transposed rows are written 16 B per lane with consecutive cg (conflict-free) and MFMA lane i reads
 // position blockbase + i (conflict-free); the position -> channel permutation is undone when the slab is stored.
 // Octet planes are padded by 32 B so the four quad lanes (four planes) of a write hit different banks.
-// One LDS stage (16.25 KB per piece pair: 48.75 KB for three pieces, 32.5 KB for two), three workgroups per CU: one
-// transposes/writes while the others multiply.  Staging units = (operand, piece): with two pieces each of the four waves
-// owns exactly one; with three, the two piece-2 units alternate between the wave pairs from step to step.
+// One LDS stage (16.25 KB per piece pair: 48.75 KB for the three pieces), three workgroups per CU: one transposes/writes while
+// the others multiply.  Staging units = (operand, piece): each of the four waves owns one of pieces 0 and 1, and the two piece-2
+// units alternate between the wave pairs from step to step.  Only the three-piece policy (SplitBf16x6) runs here: the two-piece
+// ones take conv_wgrad_split_tr_kernel.
 struct WgradCbParams {
   const void* x_cb;
   const void* dy_cb;
@@ -226,8 +227,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_split_cb_kernel(WgradCbPara
   constexpr int BM = 128, BN = 128;
   constexpr int WM = 2, WN = 2, WAVES_N = 2;
   constexpr int NP = P::NP;
-  constexpr bool EXTRA = NP == 3;          // a third piece: its two staging units alternate between the wave pairs
-  static_assert(NP == 2 || NP == 3, "two or three pieces");
+  static_assert(NP == 3, "three-piece policies");
   typedef typename P::frag frag;
   constexpr int PLANE = 130;               // 16-B units per k-octet plane (128 positions + 2 pad)
   constexpr int PIECE = 4 * PLANE;         // four octets per super-step
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_split_cb_kernel(WgradCbPara
 
   // ---- staging role of this wave: operand (0 = dY rows, 1 = X rows) and piece are wave-uniform
   const int opnd = wave & 1;
-  const int pieceA = wave >> 1;  // this wave's unit: piece 0 or 1 (a third piece alternates between the wave pairs)
+  const int pieceA = wave >> 1;  // this wave's unit: piece 0 or 1 (the third piece alternates between the wave pairs)
   const int ps = lane & 3;
   const int cg = lane >> 2;
   // source geometry of the staged operand: X is gathered through the conv geometry, dY is its own output grid
@@ -289,7 +289,7 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_split_cb_kernel(WgradCbPara
   const int sbase = (n * sC8 + ctile * 16) * sHW;  // 16-B units
   const int lane_x = ps * sS;
 
-  u32x4 R[EXTRA ? 2 : 1][8];
+  u32x4 R[2][8];
   auto issue_loads = [&](int tt, int piece, u32x4 (&dst)[8]) {
     const int ty = tt / p.tiles_x;
     const int tx = tt - ty * p.tiles_x;
@@ -332,19 +332,16 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_split_cb_kernel(WgradCbPara
   const int nsteps = t_end - t_begin;
   if (nsteps > 0) {
     issue_loads(t_begin, pieceA, R[0]);
-    if constexpr (EXTRA)
-      if ((wave >> 1) == 0) issue_loads(t_begin, 2, R[EXTRA ? 1 : 0]);
+    if ((wave >> 1) == 0) issue_loads(t_begin, 2, R[1]);
   }
   for (int s = 0; s < nsteps; ++s) {
-    const bool extra = EXTRA && (wave >> 1) == (s & 1);  // this wave pair also stages piece 2 of the step
-    if (s > 0) __syncthreads();                          // all fragment reads of the previous step are done
+    const bool extra = (wave >> 1) == (s & 1);  // this wave pair also stages piece 2 of the step
+    if (s > 0) __syncthreads();                 // all fragment reads of the previous step are done
     transpose_store(pieceA, R[0]);
-    if constexpr (EXTRA)
-      if (extra) transpose_store(2, R[EXTRA ? 1 : 0]);
+    if (extra) transpose_store(2, R[1]);
     if (s + 1 < nsteps) {
       issue_loads(t_begin + s + 1, pieceA, R[0]);
-      if constexpr (EXTRA)
-        if ((wave >> 1) == ((s + 1) & 1)) issue_loads(t_begin + s + 1, 2, R[EXTRA ? 1 : 0]);
+      if ((wave >> 1) == ((s + 1) & 1)) issue_loads(t_begin + s + 1, 2, R[1]);
     }
     __syncthreads();
     const unsigned char* a_base = smem + (lh * PLANE + wm * 64 + l31) * 16;
@@ -418,17 +415,10 @@ __device__ __forceinline__ void mcd_settle(F (&f)[A][B], int used) {
 //   <WM = 4, R = 2, NSTAGE = 3>   256 (co) x 128 (ci) tile (each wave 128 x 64), 16-pixel stages of 24 KB, three stages: the
 //                                 DMAs of tile s+2 fly while tile s multiplies -- the structure of the forward kernel's
 //                                 256 x 128 configuration, for the layers with Cout a multiple of 256
-//   <WM = 4, R = 2, NSTAGE = 3, TWO = true>   the 128-channel layers, TWO TAPS per workgroup (round 3; on request only, it measured slower --
-//                                 DESIGN 4.1c): the operand roles are swapped -- the "A" side is X
-//                                 at the shifts of taps 2 tp and 2 tp + 1 (two 128-channel blocks, exactly the big tile's two dY blocks),
-//                                 the "B" side the ONE staged dY tile both taps share -- and the workgroup computes the transposed tile
-//                                 [tap, ci][co] with the big tile's wave shape: 12 reads per 24 MFMAs, a quarter fewer DMA bytes.  The
-//                                 pieces of the cross terms are swapped with the roles, so every product and its order are those of the
-//                                 one-tap kernel: bit-identical slabs.
-template <class P, int WM, int R, int NSTAGE, bool TWO>
+// (A form with two taps per workgroup for the 128-channel layers was built and measured slower: DESIGN 4.1c.)
+template <class P, int WM, int R, int NSTAGE>
 __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbParams p) {
   static_assert(P::NP == 2, "two-piece policies");
-  static_assert(!TWO || WM == 4, "two taps = two 128-row blocks");
   constexpr int WN = 2, WAVES_N = 2;
   constexpr int BM = 64 * WM, BN = 128;
   constexpr int NP = P::NP;
@@ -451,17 +441,16 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   const int l31 = lane & 31, lh = lane >> 5;
 
   const int ci_tiles = p.ci_p / BN;
-  const int co_tiles = TWO ? p.co_p / 128 : p.co_p / BM;
+  const int co_tiles = p.co_p / BM;
   const int T_ = p.KH * p.KW;
-  const int TG = TWO ? (T_ + 1) >> 1 : T_;  // tap groups: pairs or single taps
-  const int per_split = co_tiles * ci_tiles * TG;
+  const int per_split = co_tiles * ci_tiles * T_;
   const int xcd = blockIdx.x & 7;
   const int slot = blockIdx.x >> 3;
   const int split = (slot / per_split) * 8 + xcd;
   if (split >= p.splits) return;
   int rem = slot % per_split;
-  const int tg = rem % TG;
-  rem /= TG;
+  const int tap = rem % T_;
+  rem /= T_;
   const int tile_ci = rem % ci_tiles;
   const int tile_co = rem / ci_tiles;
   const int n = split / p.chunks_per_img;
@@ -471,29 +460,30 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   int t_end = t_begin + p.tiles_per_chunk;
   if (t_end > ntiles) t_end = ntiles;
 
-  // ---- DMA role of this wave: (operand side, piece), wave-uniform.  Side 0 = the "A" rows (AB blocks of 128: dY channel blocks, or
-  // with TWO the two taps of X), side 1 = the "B" rows (one block: X at the tap, or with TWO the dY tile)
+  // ---- DMA role of this wave: (operand side, piece), wave-uniform.  Side 0 = the "A" rows (AB blocks of 128 dY channels), side 1 =
+  // the "B" rows (one block: X at the tap)
   const int opnd = wave >> 1;
   const int piece = wave & 1;
-  const bool isx = TWO ? (opnd == 0) : (opnd == 1);  // this wave stages X (gathered through the conv geometry) rather than dY
+  const bool isx = opnd == 1;  // this wave stages X (gathered through the conv geometry) rather than dY
   const int ps = lane & 3;
   const int cg = lane >> 2;
   const int sH = isx ? p.H : p.Ho;
   const int sW = isx ? p.W : p.Wo;
   const int sS = isx ? p.stride : 1;
+  // the tap's shift and validity per 128-row block (the same for every block, and tap < T_ always holds): kept in this form because it
+  // compiles to the code this kernel was measured with -- plain scalars give a different, if equivalent, prologue
   int shy[AB], shx[AB];
   bool blk_ok[AB];
 #pragma unroll
   for (int b = 0; b < AB; ++b) {
-    const int tap_b = TWO ? 2 * tg + b : tg;
-    const int ky = tap_b / p.KW, kx = tap_b - ky * p.KW;
+    const int ky = tap / p.KW, kx = tap - ky * p.KW;
     shy[b] = isx ? ky * p.dil - p.pad : 0;
     shx[b] = isx ? kx * p.dil - p.pad : 0;
-    blk_ok[b] = tap_b < T_;
+    blk_ok[b] = tap < T_;
   }
   const int sC8 = (isx ? p.Cin : p.Cout) >> 3;
-  const int cg0 = isx ? tile_ci * 16 : tile_co * (TWO ? 16 : 16 * AB);  // first channel group of the tile
-  const int nblk = opnd ? 1 : AB;                                        // 128-row blocks this wave moves per quad
+  const int cg0 = isx ? tile_ci * 16 : tile_co * 16 * AB;  // first channel group of the tile
+  const int nblk = opnd ? 1 : AB;                          // 128-row blocks this wave moves per quad
   const int sHW = sH * sW;
   // the descriptor covers this wave's PIECE and starts `bias` bytes below it so that the SGPR offset (tile + tap shift) is never negative
   const int bias = p.pad * 16 + 16;
@@ -504,7 +494,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   unsigned vconst[AB];
 #pragma unroll
   for (int b = 0; b < AB; ++b) {
-    const int cb = TWO ? cg : 16 * b + cg;  // (two taps: both blocks are the same 128 channels)
+    const int cb = 16 * b + cg;
     vconst[b] = ((cg0 + cb) < sC8 && blk_ok[b]) ? (unsigned)(cb * sHW + ps * sS) * 16u : OOB;
   }
   const int sbase = (n * sC8 + cg0) * sHW;  // 16-B units inside the piece
@@ -635,12 +625,11 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
     constexpr int SET = decltype(set_c)::value;
     // term-major (see conv_gemm_split.hip): consecutive matrix instructions go to different accumulator tiles
 #pragma unroll
-    for (int tm = 0; tm < P::NTERMS; ++tm)  // (roles swapped with TWO: the A side carries X, so the pieces swap too -- same products, same order)
+    for (int tm = 0; tm < P::NTERMS; ++tm)
 #pragma unroll
       for (int i = 0; i < WM; ++i)
 #pragma unroll
-        for (int j = 0; j < WN; ++j)
-          acc[i][j] = P::mfma(fa[SET][TWO ? P::TB[tm] : P::TA[tm]][i], fb[SET][TWO ? P::TA[tm] : P::TB[tm]][j], acc[i][j]);
+        for (int j = 0; j < WN; ++j) acc[i][j] = P::mfma(fa[SET][P::TA[tm]][i], fb[SET][P::TB[tm]][j], acc[i][j]);
   };
   // wait until at most `left` of this wave's DMAs are outstanding (left is wave-uniform: 0, NQD or NQD * AB), then barrier
   auto wait_barrier = [&](int left) {
@@ -689,36 +678,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   }
   if (s < nsteps) step(s, S0{}, S1{});
 
-  if constexpr (TWO) {  // transposed tile: rows = (tap wm, ci), columns = co -- turned through a wave-private LDS image so that the
-    // slab, laid out [co][ci] like everyone else's, is written in 256-byte runs (the loop's last barrier released the stages)
-    const int my_tap = 2 * tg + wm;
-    constexpr int PITCH = 68;  // floats per co row of the image: 16-byte aligned rows, 64 ci + padding
-    static_assert(4 * 64 * PITCH * 4 <= NSTAGE * STAGE, "four wave images fit the stage ring");
-    float* img = reinterpret_cast<float*>(smem) + wave * 64 * PITCH;
-    float* out = p.slab + ((size_t)split * T_ + (my_tap < T_ ? my_tap : 0)) * p.co_p * p.ci_p;
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh) {  // 64 ci at a time
-#pragma unroll
-      for (int i2 = 0; i2 < 2; ++i2)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int ci_l = i2 * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-#pragma unroll
-          for (int j = 0; j < WN; ++j) img[(j * 32 + l31) * PITCH + ci_l] = acc[2 * hh + i2][j][r];
-        }
-      // (one wave: its LDS writes and reads are ordered by the LDS queue)
-      if (my_tap < T_) {
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-          const int co_l = q * 4 + (lane >> 4), c4 = (lane & 15) * 4;
-          const float4 v = *reinterpret_cast<const float4*>(img + co_l * PITCH + c4);
-          *reinterpret_cast<float4*>(out + (size_t)(tile_co * 128 + wn * 64 + co_l) * p.ci_p + tile_ci * BN + hh * 64 + c4) = v;
-        }
-      }
-    }
-    return;
-  }
-  float* out = p.slab + ((size_t)split * T_ + tg) * p.co_p * p.ci_p;
+  float* out = p.slab + ((size_t)split * T_ + tap) * p.co_p * p.ci_p;
 #pragma unroll
   for (int i = 0; i < WM; ++i)
 #pragma unroll
@@ -945,23 +905,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr64_kernel(WgradCbPa
   }
 }
 
-// which pre-split kernel runs: 0 = register-transposing (three-piece policy, or MCDSEG_WGRAD_TR=0), 1 = transposed-read
-// 128x128 tiles, 2 = transposed-read 256x128 tiles
+// which pre-split kernel runs: 0 = register-transposing (three-piece policy), 1 = transposed-read 128x128 tiles, 2 = transposed-read
+// 256x128 tiles
 int mcdseg_internal_wgrad_cb_variant(const mcdseg_conv_desc* d, int math, int co_p, int ci_p, int splits) {
-  // development / test knobs (options.h), read per call so that a test can run one problem on
-  // both tile shapes: WGRAD_TR=0 = register-transposing kernel for the two-piece policy too, MCDSEG_WGRAD_BIG=0 = 128 x 128
-  // tiles only
-  const bool use_tr = mcd_opt(MCD_OPT_WGRAD_TR) != 0;
+  // development / test knob (options.h), read per call so that a test can run one problem on both tile shapes: MCDSEG_WGRAD_BIG=0 =
+  // 128 x 128 tiles only
   const bool use_big = mcd_opt(MCD_OPT_WGRAD_BIG) != 0;
-  if (!(mcd_storage_math(math) == MCDSEG_MATH_F16X3 && use_tr)) return 0;
+  if (mcd_storage_math(math) != MCDSEG_MATH_F16X3) return 0;
   // 256 x 128 tiles (16-pixel stages) for the layers whose padded Cout is a multiple of 256 -- the plan was made for 128-row
   // tiles, so the number of workgroups halves; taken only while that still fills the chip twice over
   const bool big = use_big && (co_p % 256) == 0 && (int64_t)(co_p / 256) * (ci_p / 128) * d->KH * d->KW * splits >= 1024;
-  if (big) return 2;
-  // the remaining 128-row layers with more than one tap: two taps per workgroup sharing the staged dY tile -- built, bit-identical,
-  // and SLOWER at the benchmark's sizes (256 -> 256 at N = 16: 0.309-0.349 ms against 0.286: an odd tap count idles a tenth of the waves,
-  // half as many workgroups, a transposed epilogue), so it runs only on request (MCDSEG_WGRAD_TWOTAP=1; tests)
-  return (d->KH * d->KW > 1 && mcd_opt(MCD_OPT_WGRAD_TWOTAP) != 0) ? 3 : 1;
+  return big ? 2 : 1;
 }
 
 // pre-split operands (see conv_wgrad_split_cb_kernel); chunks_per_img / splits come from the shared plan, the pixel range
@@ -974,7 +928,7 @@ int mcdseg_internal_wgrad_split_cb_launch(const mcdseg_conv_desc* d, int math, c
   p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
   p.co_p = co_p; p.ci_p = ci_p; p.chunks_per_img = chunks_per_img; p.splits = splits;
   const int variant = mcdseg_internal_wgrad_cb_variant(d, math, co_p, ci_p, splits);
-  const bool tr = variant >= 1, big = variant == 2, two = variant == 3;
+  const bool tr = variant >= 1, big = variant == 2;
   {
     const int64_t npc = mcd_math_pieces(math), nb = d->Ncb ? d->Ncb : d->N;
     const int64_t xall = (npc - 1) * nb * d->Cin * d->H * d->W * 2 + (int64_t)d->N * d->Cin * d->H * d->W * 2;
@@ -998,7 +952,7 @@ int mcdseg_internal_wgrad_split_cb_launch(const mcdseg_conv_desc* d, int math, c
   p.dy_cb_bytes = (int)yb;
   p.x_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cin * d->H * d->W * 2;  // (F16X1 reads piece 0 only)
   p.dy_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cout * d->Ho * d->Wo * 2;
-  const int64_t per_split = (int64_t)(co_p / (big ? 256 : 128)) * (ci_p / 128) * (two ? (d->KH * d->KW + 1) / 2 : d->KH * d->KW);
+  const int64_t per_split = (int64_t)(co_p / (big ? 256 : 128)) * (ci_p / 128) * d->KH * d->KW;
   const int64_t nwg = 8 * ceil_div64(splits, 8) * per_split;
   if (nwg >= (1ll << 31)) {
     mcdseg_set_error("conv_wgrad_split: grid too large");
@@ -1006,21 +960,13 @@ int mcdseg_internal_wgrad_split_cb_launch(const mcdseg_conv_desc* d, int math, c
   }
   const bool one = math == MCDSEG_MATH_F16X1;  // the same staging, one term
   if (big && one)
-    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x1, 4, 2, 3, false>), dim3((unsigned)nwg), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x1, 4, 2, 3>), dim3((unsigned)nwg), dim3(256), 0, st, p);
   else if (big)
-    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x3, 4, 2, 3, false>), dim3((unsigned)nwg), dim3(256), 0, st, p);
-  else if (two && one)
-    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x1, 4, 2, 3, true>), dim3((unsigned)nwg), dim3(256), 0, st, p);
-  else if (two)
-    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x3, 4, 2, 3, true>), dim3((unsigned)nwg), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x3, 4, 2, 3>), dim3((unsigned)nwg), dim3(256), 0, st, p);
   else if (tr && one)
-    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x1, 2, 2, 3, false>), dim3((unsigned)nwg), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x1, 2, 2, 3>), dim3((unsigned)nwg), dim3(256), 0, st, p);
   else if (tr)
-    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x3, 2, 2, 3, false>), dim3((unsigned)nwg), dim3(256), 0, st, p);
-  else if (one)
-    hipLaunchKernelGGL(conv_wgrad_split_cb_kernel<SplitF16x1>, dim3((unsigned)nwg), dim3(256), 0, st, p);
-  else if (math == MCDSEG_MATH_F16X3)
-    hipLaunchKernelGGL(conv_wgrad_split_cb_kernel<SplitF16x3>, dim3((unsigned)nwg), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((conv_wgrad_split_tr_kernel<SplitF16x3, 2, 2, 3>), dim3((unsigned)nwg), dim3(256), 0, st, p);
   else
     hipLaunchKernelGGL(conv_wgrad_split_cb_kernel<SplitBf16x6>, dim3((unsigned)nwg), dim3(256), 0, st, p);
   MCD_LAUNCH_CHECK("conv_wgrad_split_cb");

@@ -23,9 +23,7 @@
   X(WGRAD_WGS, 1024)          /* target workgroup count of the 128 / 64-tile weight-gradient plans */                        \
   X(WGRAD_THIN_TR, 1)         /* thin layers' window weight gradient */                                                      \
   X(WGRAD_TR64, 1)            /* 64 x 64 weight-gradient plan from both companions */                                        \
-  X(WGRAD_TR, 1)              /* transposed-read weight-gradient kernels (0 = register-transposing) */                       \
   X(WGRAD_BIG, 1)             /* 256 x 128 weight-gradient tiles */                                                          \
-  X(WGRAD_TWOTAP, 0)          /* two taps per workgroup (slower at the benchmark's sizes; tests) */                          \
   X(WGRAD_PP_CUS, 0)          /* weight gradient planned for this many CUs (0 = PP_CUS, else the device's) */                \
   X(WGRAD_PP, 2)              /* ping-pong weight gradient: 0 off, 1 stream-K, 2 the slab plan */                            \
   X(WGRAD_PP3, 1)             /* row-of-taps ping-pong weight gradient */                                                    \

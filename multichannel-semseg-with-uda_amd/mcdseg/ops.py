@@ -207,7 +207,6 @@ PIECES = {"f16x3": 2, "bf16x6": 3, "f16x1": 2}    # (f16x1 stores what f16x3 sto
 # small three-step trace sit at 1.7-4x the reference's own fp32-vs-fp64 spread, with the 24-bit bf16x6 direct kernel at 0.8-1.0x
 # (tools/delta_report.py) -- and the layer is 0.4 % of the step
 STEM_WINDOW = os.environ.get("MCDSEG_STEM_WINDOW", "0") != "0"
-STEM_DIRECT = os.environ.get("MCDSEG_STEM_DIRECT", "1") != "0"  # the stem's forward as the direct (bf16x6) convolution
 
 # Activation storage inside a DRN trunk (MCDSEG_ACT_STORAGE):
 #   "fp32" (default)  every fused group writes its fp32 output y next to the pre-split companion;
@@ -471,7 +470,7 @@ class PackedWeights:
         w = _req(weight.detach(), "conv weight")
         dev = w.device
         fsp, dsp = _use_split(desc.Cin), _use_split(desc.Cout)
-        direct = STEM_DIRECT and CONV_MATH in MATH_ID and bool(L.mcdseg_conv_split_direct_ok(ctypes.byref(desc)))
+        direct = CONV_MATH in MATH_ID and bool(L.mcdseg_conv_split_direct_ok(ctypes.byref(desc)))
         if direct:
             fsp = True  # the stem: direct convolution on the split path although it contracts < 16 channels
         # f32 images (kept for whichever direction does not run on the split path)
@@ -796,9 +795,8 @@ def split_companion_padded(x, bound=None):
 
 
 # mcdseg_conv_wgrad_variant code -> the kernel name rocprofv3 prints
-_WGRAD_NAMES = {10: "conv_wgrad_split_kernel<%s>", 11: "conv_wgrad_split_cb_kernel<%s>", 12: "conv_wgrad_split_tr_kernel<%s, 2, 2, 3, false>",
-                13: "conv_wgrad_split_tr_kernel<%s, 4, 2, 3, false>", 14: "conv_wgrad_split_tr64_kernel<%s>",
-                16: "conv_wgrad_split_tr_kernel<%s, 4, 2, 3, true>",
+_WGRAD_NAMES = {10: "conv_wgrad_split_kernel<%s>", 11: "conv_wgrad_split_cb_kernel<%s>", 12: "conv_wgrad_split_tr_kernel<%s, 2, 2, 3>",
+                13: "conv_wgrad_split_tr_kernel<%s, 4, 2, 3>", 14: "conv_wgrad_split_tr64_kernel<%s>",
                 17: "conv_wgrad_split_pp_kernel<%s>", 18: "conv_wgrad_split_pp3_kernel<%s>"}
 
 
@@ -893,29 +891,8 @@ def _side_stream(device):
     # measured too: 235.1 vs 236.2 ms on one box, 236.1 / 234.6 vs 234.8 / 235.0 on another; within the noise, not kept)
     key = device.index if device.index is not None else torch.cuda.current_device()
     if key not in _SIDE:
-        _SIDE[key] = _masked_stream(device, SIDE_CUS) if SIDE_CUS > 0 else torch.cuda.Stream(device=device)
+        _SIDE[key] = torch.cuda.Stream(device=device)
     return _SIDE[key]
-
-
-# MCDSEG_SIDE_CUS=n (experiment, round 5): the side stream as a HIP stream restricted to the first n compute units
-# (hipExtStreamCreateWithCUMask), so that the main stream's HBM-bound BatchNorm passes always find CUs no weight-gradient workgroup
-# holds.  0 (default): an ordinary stream.
-SIDE_CUS = int(os.environ.get("MCDSEG_SIDE_CUS", "0"))
-
-
-def _masked_stream(device, n_cus):
-    hip = ctypes.CDLL(os.path.join(os.path.dirname(torch.__file__), "lib", "libamdhip64.so"))
-    total = torch.cuda.get_device_properties(device).multi_processor_count
-    words = (total + 31) // 32
-    mask = (ctypes.c_uint32 * words)()
-    for b in range(min(n_cus, total)):
-        mask[b // 32] |= 1 << (b % 32)
-    handle = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        rc = hip.hipExtStreamCreateWithCUMask(ctypes.byref(handle), ctypes.c_uint32(words), mask)
-    if rc != 0 or not handle.value:
-        raise RuntimeError("hipExtStreamCreateWithCUMask failed (%d)" % rc)
-    return torch.cuda.ExternalStream(handle.value, device=device)
 
 
 def join_side_streams(device_index=None):

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Test infrastructure (not collected by pytest; imports the oracle like the tests do): how far are the cross-entropy gradients of
 BASELINE config 2's full batch (16 x 6 x 480 x 640, drn_d_38, train-mode BatchNorm) from the TRUTH, for the HIP path and for the
-fp32 CPU oracle?  The oracle is run twice -- in fp32 (what tests/test_model_gpu.py::test_cfg2_full_batch_vs_oracle compares with)
+fp32 CPU oracle?  The oracle is run twice -- in fp32 (what tests/test_model_gpu.py::test_cfg2_full_batch_kernels_vs_oracle compares with)
 and in fp64 on the same parameters and batch -- and the relative L2 distances oracle32-fp64, HIP-fp64 and HIP-oracle32 are printed
 per family of tensors and over all of them.  The numbers set the bounds of that test.
     python tests/grad_truth_cfg2.py [--n 16] [--math f16x3]
 ``--cfg5``: the same question for BASELINE config 5's network at its geometry -- drn_d_105 (Bottleneck), 6 x 720 x 1280, compact
 activation storage, the launch plan of its N = 32 batch (MCDSEG_PP_CUS, a batch cut along N) -- plus the distances of the encoder
-features and of the logits; sets the bounds of tests/test_model_gpu.py::test_cfg5_geometry_vs_oracle.
+features and of the logits; sets the bounds of tests/test_model_gpu.py::test_cfg5_geometry_kernels_vs_oracle.
     python tests/grad_truth_cfg2.py --cfg5 [--n 2]"""
 import argparse
 import os

@@ -773,7 +773,7 @@ def test_full_resolution_vs_oracle_and_properties():
     assert h.shape == (4, 16, 480, 640) and float(h.min()) >= 0.0
 
 
-def test_cfg2_full_batch_vs_oracle():
+def test_cfg2_full_batch_kernels_vs_oracle():
     """BASELINE config 2 at its stated size -- 16 x 6 x 480 x 640, train-mode BatchNorm, with a tape -- so that the kernels the
     benchmark times (the ping-pong and large-tile pre-split convolutions, selected only at this batch) are the ones compared: encoder
     features and logits (<= 1e-3, north_star) and the cross-entropy gradient of EVERY parameter (adapt_trainer.py:163-185) against the CPU
@@ -810,7 +810,7 @@ def test_cfg2_full_batch_vs_oracle():
             assert ops.gemm_kernel_name(128, 128, False, True, True, False, n * 60 * 80) in names, sorted(set(names))  # the 128 x 128 family
         assert ops.gemm_kernel_name(64, 64, False, True, True, False, n * 120 * 160) in names, sorted(set(names))  # the 4-wave tiles (64 rows)
         if ops.CONV_MATH == "f16x3":  # ... and the weight gradients ran on the ping-pong stream-K kernel / the 128 x 128 / 64-channel tiles
-            for wg in ("conv_wgrad_split_pp_kernel<SplitF16x3>", "conv_wgrad_split_tr_kernel<SplitF16x3, 2, 2, 3, false>",
+            for wg in ("conv_wgrad_split_pp_kernel<SplitF16x3>", "conv_wgrad_split_tr_kernel<SplitF16x3, 2, 2, 3>",
                        "conv_wgrad_split_tr64_kernel<SplitF16x3>", "conv_wgrad_thin_tr_kernel<1, 1, 25, 8>",
                        "conv_wgrad_thin_tr_kernel<2, 1, 9, 8>", "conv_wgrad_thin_tr_kernel<2, 2, 9, 4>"):
                 assert wg in names, "the backward pass did not run %s: %s" % (wg, sorted(set(names)))
@@ -1081,7 +1081,7 @@ def test_d105_bottleneck_vs_reference(golden, storage, k, monkeypatch):
         assert e <= max(k * nz, 1e-3 * float(g64[name].abs().max())), "%s: err %.3e noise %.3e" % (name, e, nz)
 
 
-def test_cfg5_geometry_vs_oracle(monkeypatch, libopt):
+def test_cfg5_geometry_kernels_vs_oracle(monkeypatch, libopt):
     """BASELINE config 5's network at ITS geometry against the truth: drn_d_105 (Bottleneck blocks,
     models/drn.py:62-100, 344-348), 2 x 6 x 720 x 1280, train-mode BatchNorm, compact activation storage -- with the launch plan of the
     stated N = 32 batch: the option PP_CUS = 16 gives the 28800 pixels of the 90 x 160 maps the rounds of tiles 460800 pixels have on 256
@@ -1125,7 +1125,7 @@ def test_cfg5_geometry_vs_oracle(monkeypatch, libopt):
     # the GEMM kernel, no weight gradient on the plans that gather fp32 (the f32 kernels keep the 41-channel seg head only)
     assert not [nm for nm in ran if nm.startswith("conv_gemm_split_kernel<") and nm.endswith("false, false>")], sorted(ran)
     assert "conv_wgrad_split_kernel<SplitF16x3>" not in ran and "conv_wgrad_split_cb_kernel<SplitF16x3>" not in ran, sorted(ran)
-    for wg in ("conv_wgrad_split_pp_kernel<SplitF16x3>", "conv_wgrad_split_tr_kernel<SplitF16x3, 2, 2, 3, false>",
+    for wg in ("conv_wgrad_split_pp_kernel<SplitF16x3>", "conv_wgrad_split_tr_kernel<SplitF16x3, 2, 2, 3>",
                "conv_wgrad_split_tr64_kernel<SplitF16x3>", "conv_wgrad_thin_tr_kernel<2, 1, 9, 8>", "conv_wgrad_thin_tr_kernel<2, 2, 9, 4>",
                # (the stem's weight gradient: its forward pass is cut along N -- here by the 150 MB limit, at N = 32 by the fp32 kernels'
                # slack rule -- but the window kernel reads the whole batch's companions, which fit one descriptor each: round 6; until

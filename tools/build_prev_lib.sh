@@ -1,6 +1,6 @@
 #!/bin/bash
-# Development tool: libmcdseg_prev.so = the kernels of another commit, for a same-box A/B in ONE gpurun call (select with MCDSEG_LIB, as
-# tools/r05o.sh / r05p.sh do).  Only the sources that differ from the working tree are compiled from that commit (with the flags of
+# Development tool: libmcdseg_prev.so = the kernels of another commit, for a same-box A/B in one GPU session (select it with
+# MCDSEG_LIB).  Only the sources that differ from the working tree are compiled from that commit (with the flags of
 # mcdseg/_lib.py: the files of NO_PACKED_F32 without packed-fp32 instructions); every other object is the current build's.
 #   bash tools/build_prev_lib.sh <commit> bn loss up8        (run `python -c "import __graft_entry__ as g; g.build()"` first)
 set -eu
