@@ -20,8 +20,11 @@ and of the forward outputs (encoder features, one head's logits) a fixed sub-sam
 The recipes (networks, seeds, batches) are those of tests/test_model_gpu.py's full-size tests.
 
     python tests/golden/make_grad_truth.py [--out DIR] cfg2 cfg3 cfg4 cfg5n2 cfg5n8
+    python tests/golden/make_grad_truth.py --lp [--out DIR] cfg5n2
 
 Run on the GPU box's host (128 cores: cfg2 takes 40 s in fp32 + 130 s in fp64); the fixtures are committed with this script.
+``--lp`` adds the low-precision yardsticks of BASELINE config 5's 2-byte chain (lowp.py; ``main_lp``) to an existing drn_d_105 fixture
+as a separate file, grad_truth_<cfg>_lp.npz.
 """
 import argparse
 import os
@@ -37,6 +40,7 @@ for p in (HERE, ROOT):
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
+import lowp  # noqa: E402
 from recipe import fill_state_, make_batch  # noqa: E402
 
 NC = 41
@@ -77,6 +81,23 @@ def record(out, name, g32, g64):
         out[name + "/s64"] = sketch(name, g64).numpy().astype(np.float32)  # (differences of interest are 1e-2 of a bucket: fp32 keeps them)
 
 
+def distance(fx, name, g):
+    """|| g - fp64 || of one gradient tensor against a fixture: exact where it keeps the tensor whole, else through its count-sketch"""
+    g = g.detach().double().cpu()
+    if name + "/x64" in fx.files:
+        return float((g - torch.from_numpy(fx[name + "/x64"]).double().reshape(g.shape)).norm())
+    return float((sketch(name, g) - torch.from_numpy(fx[name + "/s64"]).double()).norm())
+
+
+def sub_error(fx, name, t):
+    """max |t - fp64| of a forward output on the fixture's sub-sample ``<name>/sub64``"""
+    s = int(fx[name + "/stride"])
+    ref = torch.from_numpy(fx[name + "/sub64"]).double()
+    got = t.detach()[:, :, ::s, ::s].double().cpu()
+    assert got.shape == ref.shape, (name, got.shape, ref.shape)
+    return float((got - ref).abs().max())
+
+
 def record_output(out, name, o32, o64, stride):
     """a forward output: the fp32 oracle's largest error on every ``stride``-th pixel (``e32``, ``e32_stride``) and the fp64 values on a
     sub-sample of those pixels thin enough to commit (at most 100 000 values, kept as fp32: ``sub64``, ``stride``) -- the HIP path's
@@ -92,8 +113,10 @@ def record_output(out, name, o32, o64, stride):
     out[name + "/stride"] = np.int64(stride * f)
 
 
-def run_mcd(net, seeds, n, h, w, batch_seed, double):
-    """source cross-entropy pass of adapt_trainer.py:163-185 on the oracle: (features, logits of F1, {name: gradient})"""
+def run_mcd(net, seeds, n, h, w, batch_seed, double, lp=None, info=None):
+    """source cross-entropy pass of adapt_trainer.py:163-185 on the oracle: (features, logits of F1, {name: gradient}).
+    ``lp``: a low-precision yardstick of lowp.py -- "model" (the 2-byte chain's roundings inserted) or "amp" (bf16 autocast);
+    ``info`` (a dict) receives the loss and, for "amp", what autocast did"""
     from oracle import ref_loss, ref_models
     og, of1, of2 = ref_models.get_models(net, 6, NC)
     for m, s in zip((og, of1, of2), seeds):
@@ -103,10 +126,18 @@ def run_mcd(net, seeds, n, h, w, batch_seed, double):
     if double:
         og, of1, of2, src, cw = og.double(), of1.double(), of2.double(), src.double(), cw.double()
     og.train(), of1.train(), of2.train()
-    feat = og(src)
-    crit = ref_loss.CrossEntropyLoss2d(cw)
-    logits = of1(feat)
-    (crit(logits, lbl) + crit(of2(feat), lbl)).backward()
+    if lp == "model":
+        lowp.chain_model(og)
+    with torch.autocast("cpu", dtype=torch.bfloat16, enabled=lp == "amp"):
+        feat = og(src)
+        crit = ref_loss.CrossEntropyLoss2d(cw)
+        logits = of1(feat)
+        loss = crit(logits, lbl) + crit(of2(feat), lbl)
+    loss.backward()
+    if info is not None:
+        info["loss"] = float(loss.detach())
+        if lp == "amp":
+            info["recipe"] = lowp.amp_recipe(feat, logits, list(og.parameters()) + list(of1.parameters()) + list(of2.parameters()))
     gs = {"g." + k: v.grad for k, v in og.named_parameters()}
     gs.update({"f%d.%s" % (i + 1, k): v.grad for i, m in enumerate((of1, of2)) for k, v in m.named_parameters()})
     return feat.detach(), logits.detach(), gs
@@ -160,11 +191,56 @@ def run_multitask(n, double):
     return fet.detach(), float(loss.detach()), gs
 
 
+MCD_RECIPES = {"cfg2": ("drn_d_38", (11, 12, 13), 16, 480, 640, 78), "cfg5n2": ("drn_d_105", (71, 72, 73), 2, 720, 1280, 78),
+               "cfg5n8": ("drn_d_105", (71, 72, 73), 8, 720, 1280, 77)}
+
+
+def main_lp(cfg, out_dir):
+    """--lp: the low-precision yardsticks of lowp.py ("model", "amp") on the recipe of the EXISTING fixture grad_truth_<cfg>.npz, each
+    run's distance from its stored fp64 truth (no fp64 run), written to grad_truth_<cfg>_lp.npz:
+
+        <name>/dmodel, <name>/damp   || yardstick - fp64 || per gradient tensor (exact or through the sketch, as the fixture keeps it)
+        <name>/nmodel, <name>/namp   || yardstick || (where the distances saturate, the norms still tell whether a layer's gradient
+                                     has the truth's size)
+        feat/e_model, feat/e_amp, logits1/e_model, logits1/e_amp
+                                     max |yardstick - fp64| on the fixture's sub-sample (<name>/sub64)
+        loss_model, loss_amp         the two runs' losses
+        recipe_model, recipe_amp     what each run rounded"""
+    fx = np.load(os.path.join(out_dir, "grad_truth_%s.npz" % cfg))
+    net, seeds, n, h, w, bs = MCD_RECIPES[cfg]
+    names = [str(k) for k in fx["names"]]
+    out = {"recipe": fx["recipe"], "names": fx["names"]}
+    times = []
+    for lp in ("model", "amp"):
+        t0 = time.time()
+        info = {}
+        feat, logits, gs = run_mcd(net, seeds, n, h, w, bs, False, lp, info)
+        assert set(gs) == set(names), sorted(set(gs) ^ set(names))[:5]
+        for k in names:
+            out["%s/d%s" % (k, lp)] = np.float64(distance(fx, k, gs[k]))
+            out["%s/n%s" % (k, lp)] = np.float64(float(gs[k].detach().double().norm()))
+        out["feat/e_" + lp] = np.float64(sub_error(fx, "feat", feat))
+        out["logits1/e_" + lp] = np.float64(sub_error(fx, "logits1", logits))
+        out["loss_" + lp] = np.float64(info["loss"])
+        out["recipe_" + lp] = np.array(lowp.MODEL_RECIPE if lp == "model" else info["recipe"])
+        del feat, logits, gs
+        times.append(time.time() - t0)
+    path = os.path.join(out_dir, "grad_truth_%s_lp.npz" % cfg)
+    np.savez_compressed(path, **out)
+    den = sum(float(fx[k + "/n64"]) ** 2 for k in names)
+    rel = {lp: (sum(float(out["%s/d%s" % (k, lp)]) ** 2 for k in names) / den) ** 0.5 for lp in ("model", "amp")}
+    worst = max((float(out[k + "/dmodel"]) / max(float(fx[k + "/n64"]), 1e-300), k) for k in names)
+    print("%s --lp: %d tensors, model %.0f s, amp %.0f s; model - fp64 over all tensors %.3e, worst %.3e (%s); amp - fp64 %.3e; %s %.2f MB"
+          % (cfg, len(names), times[0], times[1], rel["model"], worst[0], worst[1], rel["amp"], path, os.path.getsize(path) / 1e6), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("configs", nargs="+", choices=["cfg2", "cfg3", "cfg4", "cfg5n2", "cfg5n8"])
     ap.add_argument("--out", default=HERE)
     ap.add_argument("--tiny", action="store_true", help="(smoke run of this script: 1 x 6 x 64 x 96 instead of the stated sizes)")
+    ap.add_argument("--lp", action="store_true", help="the low-precision yardsticks (lowp.py) of a drn_d_105 fixture already in --out: "
+                                                      "grad_truth_<cfg>_lp.npz; the fp64 fixture is read, not rewritten")
     args = ap.parse_args()
     if args.tiny:
         global make_batch
@@ -172,12 +248,17 @@ def main():
         make_batch = lambda seed, n, ch, h, w, nc: full(seed, 1, ch, 64, 96, nc)  # noqa: E731
     torch.set_num_threads(physical_cores())
     os.makedirs(args.out, exist_ok=True)
+    if args.lp:
+        for cfg in args.configs:
+            if cfg not in MCD_RECIPES or MCD_RECIPES[cfg][0] != "drn_d_105":
+                ap.error("--lp models the 2-byte chain of a Bottleneck DRN: cfg5n2 / cfg5n8, not %s" % cfg)
+            main_lp(cfg, args.out)
+        return
     for cfg in args.configs:
         t0 = time.time()
         out = {}
-        if cfg in ("cfg2", "cfg5n2", "cfg5n8"):
-            net, seeds, n, h, w, bs = {"cfg2": ("drn_d_38", (11, 12, 13), 16, 480, 640, 78), "cfg5n2": ("drn_d_105", (71, 72, 73), 2, 720, 1280, 78),
-                                       "cfg5n8": ("drn_d_105", (71, 72, 73), 8, 720, 1280, 77)}[cfg]
+        if cfg in MCD_RECIPES:
+            net, seeds, n, h, w, bs = MCD_RECIPES[cfg]
             f32, l32, g32 = run_mcd(net, seeds, n, h, w, bs, False)
             t1 = time.time()
             f64, l64, g64 = run_mcd(net, seeds, n, h, w, bs, True)

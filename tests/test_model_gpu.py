@@ -1000,6 +1000,13 @@ def test_cfg5_cut_batches_keep_their_companions(monkeypatch):
     assert rel(g1, "seg.weight") <= 1e-4 and rel(g1, "base.8.1.weight") <= 1e-4
 
 
+# the toy-size f16x1 case below against the low-precision yardsticks (relative L2 from fp64: features, the three named gradients; the
+# loss, one scalar, scatters more)
+D105_TWO_BYTE_K = 1.2        # in units of the model oracle's   [measured 0.97 .. 0.98]
+D105_TWO_BYTE_LOSS_K = 3.0   # ... for the loss                 [2.1]
+D105_TWO_BYTE_AMP = 1.0      # in units of bf16 autocast's      [0.38 .. 0.82; loss 0.93]
+
+
 @pytest.mark.parametrize("storage,k", [("fp32", 4.0), ("compact", 6.0), ("compact-f16x1", None)])
 def test_d105_bottleneck_vs_reference(golden, storage, k, monkeypatch):
     """drn_d_105 (Bottleneck blocks; BASELINE config 5 trunk) forward + CE backward.  105 BN layers amplify fp32
@@ -1022,20 +1029,24 @@ def test_d105_bottleneck_vs_reference(golden, storage, k, monkeypatch):
     monkeypatch.setattr(ops, "ACT_STORAGE", storage)
     from loss import CrossEntropyLoss2d
     from models.model_util import get_models
+    import lowp
     from oracle import ref_loss, ref_models
     fx = golden.npz("d105_small.npz")
     tr = golden.json("traces.json")["d105_small"]
     n, ch, h, w = tr["shape"]
     s, l, _ = make_batch(tr["seed_batch"], n, ch, h, w, NC)
 
-    def oracle(dtype):
+    def oracle(dtype, lp=None):
         ms = ref_models.get_models("drn_d_105", 6, NC)
         for m, seed in zip(ms, (71, 72, 73)):
             fill_state_(m, seed)
             m.to(dtype).train()
+        if lp == "model":
+            lowp.chain_model(ms[0])
         crit = ref_loss.CrossEntropyLoss2d(ref_loss.class_weights(NC).to(dtype))
-        feat = ms[0](s.to(dtype))
-        loss = crit(ms[1](feat), l) + crit(ms[2](feat), l)
+        with torch.autocast("cpu", dtype=torch.bfloat16, enabled=lp == "amp"):
+            feat = ms[0](s.to(dtype))
+            loss = crit(ms[1](feat), l) + crit(ms[2](feat), l)
         loss.backward()
         named = dict(ms[0].named_parameters())
         return feat.detach().double(), float(loss), {k: named[k].grad.double() for k in ("seg.weight", "base.0.0.weight", "base.5.11.conv2.weight")}
@@ -1071,6 +1082,18 @@ def test_d105_bottleneck_vs_reference(golden, storage, k, monkeypatch):
         assert relf <= 0.5 and err <= 0.5 * scale, "features: rel L2 %.3e, max err %.3e of scale %.3e" % (relf, err, scale)
         assert abs(float(loss) - l64) <= 2e-3 * abs(l64)
         assert cos["seg.weight"] >= 0.98 and min(cos.values()) >= 0.25, cos
+        # ... and against what the chain's formats cost (tests/golden/lowp.py, as test_cfg5_two_byte_chain_vs_truth at full size):
+        # the oracle with the chain's roundings ("model") and under bf16 autocast ("amp"), distances from the same fp64 run
+        yard = {lp: oracle(torch.float32, lp) for lp in ("model", "amp")}
+        dist = {lp: dict(feat=float((f - f64).norm() / f64.norm()), loss=abs(lo - l64) / abs(l64),
+                         **{nm: float((gr[nm] - g64[nm]).norm() / g64[nm].norm()) for nm in g64}) for lp, (f, lo, gr) in yard.items()}
+        hip = dict(feat=relf, loss=abs(float(loss) - l64) / abs(l64), **relg)
+        print("f16x1 on drn_d_105, relative distances from fp64: HIP %s, model %s, amp %s" % (hip, dist["model"], dist["amp"]))
+        for key, d in hip.items():
+            floor = 2e-5 if key == "loss" else 0.0
+            k_model = D105_TWO_BYTE_LOSS_K if key == "loss" else D105_TWO_BYTE_K
+            assert d <= k_model * dist["model"][key] + floor, "%s: HIP %.3e, model %.3e" % (key, d, dist["model"][key])
+            assert d <= D105_TWO_BYTE_AMP * dist["amp"][key] + floor, "%s: HIP %.3e, amp %.3e" % (key, d, dist["amp"][key])
         return
     assert err <= max(k * noise, 2e-5 * scale), "feat err %.3e, fp32-oracle noise %.3e, scale %.3e" % (err, noise, scale)
     assert abs(float(loss) - l64) <= max(k * abs(l32 - l64), 1e-5 * abs(l64))
@@ -1136,6 +1159,84 @@ def test_cfg5_geometry_kernels_vs_oracle(monkeypatch, libopt):
     dist = truth.distances(fx, grads)
     for k in ("f1.up.weight", "f2.up.weight"):
         assert dist[k][0] <= 2e-4 * dist[k][2], "%s: %.3e of its norm" % (k, dist[k][0] / dist[k][2])
+
+
+# BASELINE config 5 in its stated dtype (``bench.py --dtype f16``: the 2-byte chain) against the same fp64 truth, in units of what its
+# FORMATS cost on the oracle (tests/golden/grad_truth_cfg5n2_lp.npz; make_grad_truth.py --lp, tests/golden/lowp.py): "model" = the fp32
+# oracle with the chain's roundings inserted, "amp" = the oracle under bf16 autocast.  Measured values in brackets
+# (profiles/truth_report_two_byte.txt).
+TWO_BYTE_OVERALL = 1.2       # HIP - fp64 over all gradient tensors, in units of model - fp64                  [measured 1.01]
+TWO_BYTE_P90 = 1.2           # ... for 90 % of the single tensors                                              [1.05]
+TWO_BYTE_PER_TENSOR = 1.35   # ... the worst tensor                                                            [1.15]
+TWO_BYTE_OUTPUT = 1.3        # max |HIP - fp64| of feat / logits1 on the sub-sample, in units of the model's   [0.88, 1.01]
+TWO_BYTE_LOSS = 1e-4         # |loss HIP - loss model| / loss model                                            [1.9e-5; amp 3.7e-5]
+TWO_BYTE_LOGNORM = 1.2       # max over tensors of |log(|HIP grad| / |fp64 grad|)|, in units of the model's    [0.94]
+
+
+def test_cfg5_two_byte_chain_vs_truth(monkeypatch, libopt):
+    """BASELINE config 5 AS STATED -- CONV_MATH=f16x1, compact storage, the 2-byte chain (ops.HALF_STORAGE: z as scaled fp16, the
+    activation as the leading companion piece, gradients between the groups as bf16) -- at its geometry, drn_d_105 2 x 6 x 720 x 1280,
+    with the launch plan of the stated N = 32 emulated as in ``test_cfg5_geometry_kernels_vs_oracle`` (PP_CUS = 16, 150 MB launch
+    limit).  No batch of the CHAIN is cut at this size: its launches address 16-bit operands, 59 MB per image of the widest (2048 x
+    90 x 160) map, so the 150 MB limit leaves N = 2 whole (asserted; the fp32-gather cut path is test_cfg5_geometry_kernels_vs_oracle's).
+    Every one of the 328 gradients against the fp64 truth (``truth.report_lp``): within a small multiple of the ``model`` yardstick
+    overall, at p90 and per tensor; overall no further than bf16 autocast is (what BASELINE's "bf16" promises); noise-only tensors
+    vanish.  G's output ``feat`` is the seg head's fp32 result (the trunk's last layer and the head are outside the chain: not a
+    virtual bf16 tensor, asserted) and is compared as it is.
+    Through 105 train-mode BatchNorms at random initialisation a 16-bit chain's gradient DIRECTIONS decorrelate from the truth: the
+    model yardstick itself is 1.24 of the gradients' norm from fp64 (amp 1.44, the fp32 oracle 0.058), so the distance bounds are
+    wide in absolute terms and only catch a path that is worse than chance.  The gradients' SIZES do not decorrelate: every tensor's
+    |log(|HIP| / |fp64|)| is bounded by a multiple of the model's worst -- a wrong factor in one scale or a wrong ReLU mask changes
+    a layer's gradient norm (what that resolves is stated in the PR that added this test: CPU mutations of the model)."""
+    dev = _dev()
+    import truth
+    from mcdseg import ops
+    monkeypatch.setattr(ops, "CONV_MATH", "f16x1")
+    monkeypatch.setattr(ops, "ACT_STORAGE", "compact")
+    monkeypatch.setattr(ops, "HALF_STORAGE", True)
+    monkeypatch.setattr(ops, "MAX_CONV_BYTES", 150 << 20)
+    libopt(PP_CUS=16)
+    for shape in ((2, 2048, 90, 160), (2, 512, 90, 160)):
+        d = ops.conv_desc(shape, (512, shape[1], 1, 1), 1, 0, 1)
+        assert len(ops._batch_pieces_half(d)) == 1, shape
+    names = []
+    timer_prev = ops.LAUNCH_TIMER
+
+    class _Names:
+        def wants(self, name):
+            names.append(name)
+            return False
+    ops.LAUNCH_TIMER = _Names()
+    try:
+        outs, grads = truth.hip_run("cfg5n2", dev)
+    finally:
+        ops.LAUNCH_TIMER = timer_prev
+    ran = set(names)
+    for nm in ("bn_apply_half", "bn_bwd_reduce_half", "bn_bwd_apply_half"):
+        assert nm in ran, "the pass did not run %s: %s" % (nm, sorted(ran))
+    assert any("SplitF16x1D" in nm for nm in ran), sorted(ran)
+    assert not [nm for nm in ran if "SplitF16x3" in nm], sorted(ran)
+    assert not ops.is_half(outs["feat"]) and outs["feat"].dtype == torch.float32
+    fx, lpx = truth.load("cfg5n2"), truth.load_lp("cfg5n2")
+    lines, res = truth.report_lp("cfg5n2", outs, grads, fx, lpx)
+    print("\n".join(lines))
+    m, a = res["model"], res["amp"]
+    assert m["overall"] <= TWO_BYTE_OVERALL, "all gradients %.2fx the model's distance from the truth" % m["overall"]
+    assert m["p90"] <= TWO_BYTE_P90, "the 90th percentile of the per-tensor ratios is %.2fx the model's" % m["p90"]
+    assert m["worst"] <= TWO_BYTE_PER_TENSOR, "%s is %.2fx the model's distance from the truth" % (m["wname"], m["worst"])
+    assert a["overall"] <= 1.0, "all gradients %.2fx bf16 autocast's distance from the truth" % a["overall"]
+    total = sum(n * n for _, _, n in m["dist"].values()) ** 0.5
+    for name, d, _, _ in m["noise"]:
+        assert d <= 1e-6 * total, "%s should vanish, has norm %.3e of %.3e" % (name, d, total)
+    for name in ("feat", "logits1"):
+        e = truth.output_error(fx, name, outs[name])[0]
+        assert e <= TWO_BYTE_OUTPUT * float(lpx[name + "/e_model"]), "%s: max |HIP - fp64| %.3e, the model's %.3e" % (name, e, float(lpx[name + "/e_model"]))
+    lm = float(lpx["loss_model"])
+    assert abs(outs["loss"] - lm) <= TWO_BYTE_LOSS * abs(lm), "loss %.6f, the model's %.6f" % (outs["loss"], lm)
+    hip_ln, model_ln = res["lognorm"]["HIP"], res["lognorm"]["model"]
+    assert hip_ln[0] <= TWO_BYTE_LOGNORM * model_ln[0], "%s: |log(|HIP| / |fp64|)| %.3f, the model's worst %.3f" % (hip_ln[1], hip_ln[0], model_ln[0])
+    del outs, grads
+    torch.cuda.empty_cache()
 
 
 def test_cfg5_at_eight_pairs_vs_oracle(monkeypatch):
