@@ -341,6 +341,29 @@ int mcdseg_up8_softmax_ce_l1(const float* s1, const float* w1, const float* s2, 
                              const float* class_weight, int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in,
                              float* g1, float* g2, float* losses, int32_t N, int32_t C, int32_t Hi, int32_t Wi,
                              void* workspace, size_t workspace_bytes, void* stream);
+/* The same two passes with the classifier discrepancy of the reference's --d_loss (argmyparse.py, loss.py:192-210) in place of the L1
+ * distance: losses[2] = the distance, g_k = ce_coef * dCE_k/dz_k + diff_coef * dDist/dz_k.  With p = softmax(z1), q = softmax(z2) and the
+ * element mean over N*C*H*W that every one of these criteria uses:
+ *   MCDSEG_DIST_L1         mean |p - q|                                  Diff2d                            loss.py:93-100
+ *   MCDSEG_DIST_SYMKL      mean 0.5 (p - q)(log p - log q)               Symkl2d, MySymkl2d                loss.py:103-118, 144-154
+ *   MCDSEG_DIST_MIS_SYMKL  mean 0.5 (p log p + q log q - 2 p q)          MisSymKLD, SpatialJSD2d           loss.py:66-75, 157-173
+ *   MCDSEG_DIST_JSD        mean 0.5 (p log(p/m) + q log(q/m)), m = softmax((z1 + z2) / 2)        JSD       loss.py:78-89
+ * Arguments as mcdseg_softmax_ce_l1 / mcdseg_up8_softmax_ce_l1 (workspaces included) plus dist_kind.  MCDSEG_DIST_L1 launches the kernels
+ * of those entry points (bitwise the same results); the other kinds are distances between two heads: z2 (s2, w2) must not be NULL.
+ * An unknown dist_kind is an argument error.  The fused form launches `up8_softmax_ce_dist_dma_kernel<classes, exact, kind>` where
+ * mcdseg_up8_loss_variant is positive and `up8_softmax_ce_dist_kernel<classes, kind>` where it is negative. */
+#define MCDSEG_DIST_L1 0
+#define MCDSEG_DIST_SYMKL 1
+#define MCDSEG_DIST_MIS_SYMKL 2
+#define MCDSEG_DIST_JSD 3
+int mcdseg_softmax_ce_dist(const float* z1, const float* z2, const int64_t* labels, const float* class_weight,
+                           int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in,
+                           float* g1, float* g2, float* losses,
+                           int32_t N, int32_t C, int32_t HW, int32_t dist_kind, void* workspace, size_t workspace_bytes, void* stream);
+int mcdseg_up8_softmax_ce_dist(const float* s1, const float* w1, const float* s2, const float* w2, const int64_t* labels,
+                               const float* class_weight, int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in,
+                               float* g1, float* g2, float* losses, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t dist_kind,
+                               void* workspace, size_t workspace_bytes, void* stream);
 /* out[0] = sum_i w[labels_i] over P pixels (ignore_index and out-of-range labels contribute 0) */
 size_t mcdseg_label_weight_sum_workspace_bytes(int64_t P);
 int mcdseg_label_weight_sum(const int64_t* labels, const float* class_weight, int64_t ignore_index, int32_t C, int64_t P,

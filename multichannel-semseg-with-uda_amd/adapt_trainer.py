@@ -132,7 +132,7 @@ def main(argv=None):
             fix_batchnorm_when_training(m)
 
     solver = None
-    if args.solver == "fused" and args.d_loss == "diff":
+    if args.solver == "fused":  # whatever --d_loss: every distance is a kind of the fused loss kernels
         solver = MCDSolver(model_g, model_f1, model_f2, optimizer_g, optimizer_f, criterion, criterion_d, num_k=args.num_k,
                            num_multiply_d_loss=args.num_multiply_d_loss)
 

@@ -101,7 +101,11 @@ def get_da_mcd_training_parser():
     parser.add_argument("--num_k", type=int, default=4, help="how many steps to repeat the generator update")
     parser.add_argument("--num_multiply_d_loss", type=int, default=1)
     parser.add_argument("--d_loss", type=str, default="diff",
-                        choices=["jsd", "mysymkl", "spatial_jsd", "symkl", "diff", "nmlsymkl", "strange_kl", "mis_symkl"])
+                        choices=["jsd", "mysymkl", "spatial_jsd", "symkl", "diff", "nmlsymkl", "strange_kl", "mis_symkl"],
+                        help="classifier discrepancy of steps B and C (loss.py:192-210): diff = mean |p1 - p2| (default); symkl / nmlsymkl / "
+                             "mysymkl = symmetric KL; mis_symkl / spatial_jsd = the reference's kl_div on probabilities; jsd = Jensen-Shannon "
+                             "about the softmax of the mean logits.  All of them run inside the fused HIP loss kernels "
+                             "(strange_kl has no criterion in the reference either)")
     parser.add_argument("--uses_one_classifier", action="store_true", help="separate f1, f2")
     return parser
 

@@ -134,50 +134,125 @@ __device__ __forceinline__ void pixel_losses(float (&a)[NCMAX], float (&b)[NCMAX
   }
 }
 
-template <int NCMAX, bool TWO>
-__global__ __launch_bounds__(256) void softmax_ce_l1_kernel(const float* __restrict__ z1, const float* __restrict__ z2,
-                                                            const int64_t* __restrict__ labels, const float* __restrict__ cw,
-                                                            int64_t ignore_index, float ce_coef, float diff_coef,
-                                                            const float* __restrict__ losses_w, float* __restrict__ g1,
-                                                            float* __restrict__ g2, float* __restrict__ part, int C, int HW,
-                                                            int64_t P, float inv_m) {
-  const int64_t pix = blockIdx.x * (int64_t)LOSS_BLOCK + threadIdx.x;
-  const bool valid = pix < P;
-  float ce1 = 0.f, ce2 = 0.f, dsum = 0.f;
-  if (valid) {
-    const int64_t n = pix / HW;
-    const int hw = (int)(pix - n * HW);
-    const size_t base = (size_t)n * C * HW + hw;
-    float a[NCMAX], b[NCMAX];
+// ---- the probability distances of --d_loss besides L1 (loss.py:66-189) -------------------------------------
+// With p = softmax(z1), q = softmax(z2), lp = log p, lq = log q, all under the element mean 1/M that Diff2d uses:
+//   SYMKL      0.5 (p - q)(lp - lq)                 Symkl2d / MySymkl2d       loss.py:103-118, 144-154
+//   MIS_SYMKL  0.5 (p lp + q lq - 2 p q)            MisSymKLD / SpatialJSD2d  loss.py:66-75, 157-173
+//   JSD        0.5 (p (lp - lm) + q (lq - lm)),  m = softmax((z1 + z2) / 2)   JSD  loss.py:78-89
+// d/dz1_k = (1/M) (p_k u_k - p_k S + J_k),  S = sum_c p_c u_c,  u = d summand / dp:
+//   SYMKL      p u = 0.5 (p (lp - lq) + (p - q))    (in this form nothing divides by a probability that flushed to zero)
+//   MIS_SYMKL    u = 0.5 (lp + 1 - 2 q)
+//   JSD          u = 0.5 (lp - lm)   (the "+ 1" of d(p lp)/dp is a constant, and p_k (const - sum_c p_c const) = 0: left out, identical
+//                                     heads then give zeros exactly),   J_k = -0.25 (p_k + q_k - 2 m_k): the path through the mean logits
+// and d/dz2 by symmetry (J is the same for both heads).
+// a[] / b[] KEEP the logits: a probability and its logarithm are both needed per class and pass, and four arrays of NCMAX floats do not
+// fit beside the up-sampler's state.  lp_c = z_c - (max + log sum) -- one logf per pixel and head, never log(p_c) -- and
+// p_c = exp_nonpos(z_c - max) / sum is recomputed where it is used (two instructions and a multiply; the same expression as
+// pixel_losses, so the cross-entropy terms are bitwise those of the L1 kernels).  Padding classes c >= C carry -inf, and 0 * -inf is
+// NaN: unlike the L1 terms these multiply by log-probabilities, so the value loop carries the c < C guard too.
+enum { DIST_L1 = MCDSEG_DIST_L1, DIST_SYMKL = MCDSEG_DIST_SYMKL, DIST_MIS_SYMKL = MCDSEG_DIST_MIS_SYMKL, DIST_JSD = MCDSEG_DIST_JSD };
+
+template <int NCMAX, int KIND>
+__device__ __forceinline__ void pixel_dist(float (&a)[NCMAX], float (&b)[NCMAX], int y, float wy, float ce_coef, float diff_coef,
+                                           const float* __restrict__ losses_w, float* __restrict__ g1, float* __restrict__ g2,
+                                           size_t base, size_t HW, int C, float inv_m, float& ce1, float& ce2, float& dsum) {
+  constexpr bool JS = KIND == DIST_JSD;
+  float m1 = a[0], m2 = b[0], m3 = JS ? 0.5f * (a[0] + b[0]) : 0.f;
 #pragma unroll
-    for (int c = 0; c < NCMAX; ++c) {
-      a[c] = (c < C) ? z1[base + (size_t)c * HW] : -INFINITY;
-      b[c] = (TWO && c < C) ? z2[base + (size_t)c * HW] : -INFINITY;
-    }
-    int y = -1;
-    float wy = 0.f;
-    if (labels != nullptr) {
-      const int64_t yl = labels[pix];
-      if (yl != ignore_index && yl >= 0 && yl < C) {
-        y = (int)yl;
-        wy = cw ? cw[y] : 1.f;
+  for (int c = 1; c < NCMAX; ++c) {
+    m1 = fmaxf(m1, a[c]);
+    m2 = fmaxf(m2, b[c]);
+    if (JS) m3 = fmaxf(m3, 0.5f * (a[c] + b[c]));
+  }
+  float s1 = 0.f, s2 = 0.f, s3 = 0.f, zy1 = 0.f, zy2 = 0.f;
+#pragma unroll
+  for (int c0 = 0; c0 < NCMAX; c0 += 4) {
+    MCD_OPAQUE_TRUE(go);
+    if (go) {
+#pragma unroll
+      for (int c = c0; c < c0 + 4; ++c) {
+        if (c >= NCMAX) continue;
+        if (c == y) {
+          zy1 = a[c];
+          zy2 = b[c];
+        }
+        s1 += exp_nonpos(a[c] - m1);
+        s2 += exp_nonpos(b[c] - m2);
+        if (JS) s3 += exp_nonpos(0.5f * (a[c] + b[c]) - m3);
       }
     }
-    pixel_losses<NCMAX, TWO>(a, b, y, wy, ce_coef, diff_coef, losses_w, g1, g2, base, (size_t)HW, C, inv_m, ce1, ce2, dsum);
   }
-  __shared__ float sh[3][4];
-  ce1 = wave_sum(ce1);
-  ce2 = wave_sum(ce2);
-  dsum = wave_sum(dsum);
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = ce1;
-    sh[1][threadIdx.x >> 6] = ce2;
-    sh[2][threadIdx.x >> 6] = dsum;
+  const float L1 = m1 + logf(s1), L2 = m2 + logf(s2), L3 = JS ? m3 + logf(s3) : 0.f;
+  if (y >= 0) {
+    ce1 = wy * (L1 - zy1);
+    ce2 = wy * (L2 - zy2);
   }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int q = threadIdx.x;
-    part[(size_t)blockIdx.x * 3 + q] = (sh[q][0] + sh[q][1]) + (sh[q][2] + sh[q][3]);
+  const float r1 = 1.f / s1, r2 = 1.f / s2, r3 = JS ? 1.f / s3 : 0.f;
+  // p u of head 1 and q u of head 2 for class c (and, JSD, the third softmax)
+  auto terms = [&](int c, float& p, float& q, float& pu, float& qu, float& pm) {
+    p = exp_nonpos(a[c] - m1) * r1;
+    q = exp_nonpos(b[c] - m2) * r2;
+    const float lp = a[c] - L1, lq = b[c] - L2;
+    pm = 0.f;
+    if (KIND == DIST_SYMKL) {
+      const float dl = lp - lq, dp = p - q;
+      pu = 0.5f * (p * dl + dp);
+      qu = 0.5f * (-dp - q * dl);
+    } else if (KIND == DIST_MIS_SYMKL) {
+      pu = p * (0.5f * ((lp + 1.f) - 2.f * q));
+      qu = q * (0.5f * ((lq + 1.f) - 2.f * p));
+    } else {
+      const float zm = 0.5f * (a[c] + b[c]);
+      const float lm = zm - L3;
+      pm = exp_nonpos(zm - m3) * r3;
+      pu = p * (0.5f * (lp - lm));
+      qu = q * (0.5f * (lq - lm));
+    }
+  };
+  float t1 = 0.f, t2 = 0.f;
+#pragma unroll
+  for (int c0 = 0; c0 < NCMAX; c0 += 4) {
+    MCD_OPAQUE_TRUE(go);
+    if (go) {
+#pragma unroll
+      for (int c = c0; c < c0 + 4; ++c) {
+        if (c >= NCMAX) continue;
+        if (c < C) {
+          float p, q, pu, qu, pm;
+          terms(c, p, q, pu, qu, pm);
+          t1 += pu;
+          t2 += qu;
+          if (KIND == DIST_SYMKL)
+            dsum += 0.5f * ((p - q) * ((a[c] - L1) - (b[c] - L2)));
+          else if (KIND == DIST_MIS_SYMKL)
+            dsum += 0.5f * ((p * (a[c] - L1) + q * (b[c] - L2)) - 2.f * (p * q));
+          else
+            dsum += pu + qu;
+        }
+      }
+    }
+  }
+  if (g1 != nullptr || g2 != nullptr) {
+    const float kce = (ce_coef != 0.f && y >= 0) ? ce_coef * wy / losses_w[3] : 0.f;
+    const float kd = diff_coef * inv_m;
+#pragma unroll
+    for (int c0 = 0; c0 < NCMAX; c0 += 4) {
+      MCD_OPAQUE_TRUE(go);
+      if (go) {
+#pragma unroll
+        for (int c = c0; c < c0 + 4; ++c) {
+          if (c >= NCMAX) continue;
+          if (c < C) {
+            const float oh = (c == y) ? 1.f : 0.f;
+            float p, q, pu, qu, pm;
+            terms(c, p, q, pu, qu, pm);
+            const float j = JS ? -0.25f * ((p + q) - 2.f * pm) : 0.f;
+            if (g1 != nullptr) g1[base + (size_t)c * HW] = kce * (p - oh) + kd * ((pu - p * t1) + j);
+            if (g2 != nullptr) g2[base + (size_t)c * HW] = kce * (q - oh) + kd * ((qu - q * t2) + j);
+          }
+        }
+      }
+    }
   }
 }
 
@@ -193,145 +268,6 @@ __global__ __launch_bounds__(256) void softmax_ce_l1_kernel(const float* __restr
 // the losses' summands and the gradients equal the two-pass result bit for bit; only the summation order of the loss
 // values differs (per lane over its items, then the block, then fp64 over blocks).
 constexpr int UP_COLS = 64, UP_JP = 9, UP_NT = 512;  // UP_JP: input-column pairs (ix-1, ix) a 64-pixel row segment touches
-
-template <int NCMAX, bool TWO>
-__global__ __launch_bounds__(UP_NT) void up8_softmax_ce_l1_kernel(const float* __restrict__ s1, const float* __restrict__ w1,
-                                                                  const float* __restrict__ s2, const float* __restrict__ w2,
-                                                                  const int64_t* __restrict__ labels, const float* __restrict__ cw,
-                                                                  int64_t ignore_index, float ce_coef, float diff_coef,
-                                                                  const float* __restrict__ losses_w, float* __restrict__ g1,
-                                                                  float* __restrict__ g2, float* __restrict__ part, int N, int C,
-                                                                  int Hi, int Wi, float inv_m) {
-  extern __shared__ __attribute__((aligned(16))) float up_sm[];
-  constexpr int HEADS = TWO ? 2 : 1;
-  constexpr int SREG = (HEADS * NCMAX * UP_JP * 4 + UP_NT - 1) / UP_NT;  // staged scores per thread and item
-  // Class stride NCMAX, not C, and the four taps / four scores of a pixel as one 16-byte unit: every LDS read below is then
-  // the lane's base address plus an immediate offset.  (With C in the stride, or with the scores as plain rows read by
-  // ds_read2_b32 -- whose offset field reaches 1 KB -- the 2 x NCMAX addresses become registers of their own and the
-  // kernel spills hundreds of them.)
-  float* wl = up_sm;                         // [head][NCMAX][ky0 8][kx0 8][a 2][b 2]
-  float* sin = up_sm + HEADS * NCMAX * 256;  // [head][NCMAX][pair UP_JP][a 2][b 2]: score (row iyg - a, column ixb + pair + 1 - b)
-  const int Wo = 8 * Wi, Ho = 8 * Hi;
-  const int nseg = (Wo + UP_COLS - 1) / UP_COLS;
-  const int items = N * (Hi + 1) * nseg;
-  const int ky0 = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int i = threadIdx.x; i < HEADS * NCMAX * 256; i += UP_NT) {
-    const int b = i & 1, a = (i >> 1) & 1, kx = (i >> 2) & 7, ky = (i >> 5) & 7, hc = i >> 8;
-    const int c = hc % NCMAX;
-    // classes past C: taps (1, 0, 0, 0) against scores (-inf, 0, 0, 0) below give the logit -inf with no test in the pixel loop
-    wl[i] = c < C ? (hc >= NCMAX ? w2 : w1)[c * 256 + (ky + 8 * a) * 16 + kx + 8 * b] : ((a | b) == 0 ? 1.f : 0.f);
-  }
-  constexpr int nstage = HEADS * NCMAX * UP_JP * 4;
-  float sreg[SREG];
-  auto fetch = [&](int item) {  // scores of one item -> registers (zeros outside the map)
-    const int seg = item % nseg, r = item / nseg;
-    const int iyg = r % (Hi + 1), n = r / (Hi + 1);
-    const int ixb = seg * (UP_COLS / 8) - 1;
-#pragma unroll
-    for (int k = 0; k < SREG; ++k) {
-      const int i = threadIdx.x + k * UP_NT;
-      float v = 0.f;
-      if (i < nstage) {
-        const int b = i & 1, a = (i >> 1) & 1, q = i >> 2;
-        const int j = q % UP_JP, hc = q / UP_JP;
-        const int c = hc % NCMAX;
-        const int iy = iyg - a, ix = ixb + j + 1 - b;
-        if (c >= C)
-          v = (a | b) == 0 ? -INFINITY : 0.f;
-        else if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi)
-          v = (hc >= NCMAX ? s2 : s1)[(((size_t)n * C + c) * Hi + iy) * Wi + ix];
-      }
-      sreg[k] = v;
-    }
-  };
-  float ce1 = 0.f, ce2 = 0.f, dsum = 0.f;
-  int item = blockIdx.x;
-  if (item < items) fetch(item);
-  for (; item < items; item += gridDim.x) {
-    __syncthreads();  // the previous item's readers are done (and, first time round, the kernels are staged)
-#pragma unroll
-    for (int k = 0; k < SREG; ++k) {
-      const int i = threadIdx.x + k * UP_NT;
-      if (i < nstage) sin[i] = sreg[k];
-    }
-    __syncthreads();
-    if (item + (int)gridDim.x < items) fetch(item + gridDim.x);
-    const int seg = item % nseg, r = item / nseg;
-    const int iyg = r % (Hi + 1), n = r / (Hi + 1);
-    const int oy = 8 * iyg - 4 + ky0;
-    const int ox = seg * UP_COLS + lane;
-    if (oy >= 0 && oy < Ho && ox < Wo) {
-      // the class count re-read as an opaque scalar: otherwise the NCMAX "c < C" store guards are hoisted out of the item loop
-      // and their results spill
-      int Cv = C;
-      asm volatile("" : "+s"(Cv));
-      const int kx0 = (ox + 4) & 7;
-      const int jp = ((ox + 4) >> 3) - seg * (UP_COLS / 8);  // pair whose b = 0 member is this pixel's right-hand input column
-      // the lane's LDS offsets, opaque too: the kernel taps do not depend on the item ((ox + 4) & 7 is the lane's), and left
-      // alone the compiler hoists all 2 x NCMAX 16-byte reads out of the item loop
-      int woff = (ky0 * 8 + kx0) * 4, soff = jp * 4;
-      asm volatile("" : "+v"(woff), "+v"(soff));
-      float a[NCMAX], b[NCMAX];
-#pragma unroll
-      for (int c0 = 0; c0 < NCMAX; c0 += 4) {
-        MCD_OPAQUE_TRUE(go);  // groups of four classes in basic blocks of their own (see pixel_losses)
-        if (go) {
-#pragma unroll
-          for (int c = c0; c < c0 + 4; ++c) {
-            if (c >= NCMAX) continue;
-            b[c] = -INFINITY;
-#pragma unroll
-            for (int h = 0; h < HEADS; ++h) {
-              const float4 wv = *reinterpret_cast<const float4*>(wl + woff + (h * NCMAX + c) * 256);
-              const float4 sv = *reinterpret_cast<const float4*>(sin + soff + (h * NCMAX + c) * (UP_JP * 4));
-              float o = 0.f;
-              o = fmaf(sv.x, wv.x, o);
-              o = fmaf(sv.y, wv.y, o);
-              o = fmaf(sv.z, wv.z, o);
-              o = fmaf(sv.w, wv.w, o);
-              if (h == 0)
-                a[c] = o;
-              else
-                b[c] = o;
-            }
-          }
-        }
-      }
-      const size_t HW = (size_t)Ho * Wo;
-      const size_t hw = (size_t)oy * Wo + ox;
-      int y = -1;
-      float wy = 0.f;
-      if (labels != nullptr) {
-        const int64_t yl = labels[(size_t)n * HW + hw];
-        if (yl != ignore_index && yl >= 0 && yl < C) {
-          y = (int)yl;
-          wy = cw ? cw[y] : 1.f;
-        }
-      }
-      float e1 = 0.f, e2 = 0.f, ds = 0.f;
-      pixel_losses<NCMAX, TWO>(a, b, y, wy, ce_coef, diff_coef, losses_w, g1, g2, (size_t)n * C * HW + hw, HW, Cv, inv_m, e1, e2, ds);
-      ce1 += e1;
-      ce2 += e2;
-      dsum += ds;
-    }
-  }
-  __shared__ float sh[3][UP_NT / 64];
-  ce1 = wave_sum(ce1);
-  ce2 = wave_sum(ce2);
-  dsum = wave_sum(dsum);
-  if (lane == 0) {
-    sh[0][ky0] = ce1;
-    sh[1][ky0] = ce2;
-    sh[2][ky0] = dsum;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int q = threadIdx.x;
-    float t = 0.f;
-    for (int k = 0; k < UP_NT / 64; ++k) t += sh[q][k];
-    part[(size_t)blockIdx.x * 3 + q] = t;
-  }
-}
 
 // ---- the same kernel with nothing between an item's stores and the next item's inputs ----------------------------------------
 // The kernel above fetches the next item's scores into registers (and reads labels and class weights from memory inside the item):
@@ -361,149 +297,40 @@ struct UpDmaLayout {
   static constexpr size_t BYTES = (size_t)(W_FLOATS + S_FLOATS + CW_FLOATS) * 4 + LAB_BYTES;
 };
 
-template <int NCMAX, bool TWO, bool EXACT>
-__global__ __launch_bounds__(UP_NT) void up8_softmax_ce_l1_dma_kernel(const float* __restrict__ s1, const float* __restrict__ w1,
-                                                                      const float* __restrict__ s2, const float* __restrict__ w2,
-                                                                      const int64_t* __restrict__ labels, const float* __restrict__ cw,
-                                                                      int64_t ignore_index, float ce_coef, float diff_coef,
-                                                                      const float* __restrict__ losses_w, float* __restrict__ g1,
-                                                                      float* __restrict__ g2, float* __restrict__ part, int N, int C,
-                                                                      int Hi, int Wi, float inv_m) {
-  extern __shared__ __attribute__((aligned(16))) float up_sm[];
-  using L = UpDmaLayout<NCMAX, TWO>;
-  constexpr int HEADS = L::HEADS, SPK = L::SPK, SP = L::SP;
-  float* wl = up_sm;                                                   // [head][NCMAX][ky0 8][kx0 8][a 2][b 2]
-  float* sin0 = up_sm + L::W_FLOATS;                                   // [buffer 2][head][SP]: [NCMAX][pair UP_JP][a 2][b 2] + tail
-  float* cwl = sin0 + L::S_FLOATS;                                     // [NCMAX] class weights (1 without)
-  unsigned char* lab0 = reinterpret_cast<unsigned char*>(cwl + L::CW_FLOATS);  // [buffer 2][wave 8][1 KB]
-  const int Wo = 8 * Wi, Ho = 8 * Hi;
-  const int nseg = (Wo + UP_COLS - 1) / UP_COLS;
-  const int items = N * (Hi + 1) * nseg;
-  const int lane = threadIdx.x & 63;
-  const int ky0 = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  for (int i = threadIdx.x; i < HEADS * NCMAX * 256; i += UP_NT) {
-    const int b = i & 1, a = (i >> 1) & 1, kx = (i >> 2) & 7, ky = (i >> 5) & 7, hc = i >> 8;
-    const int c = hc % NCMAX;
-    wl[i] = c < C ? (hc >= NCMAX ? w2 : w1)[c * 256 + (ky + 8 * a) * 16 + kx + 8 * b] : 0.f;
-  }
-  for (int i = threadIdx.x; i < NCMAX; i += UP_NT) cwl[i] = (cw != nullptr && i < C) ? cw[i] : 1.f;
-  const mcd_i32x4 rs1 = mcd_raw_rsrc(s1, N * C * Hi * Wi * 4);
-  const mcd_i32x4 rs2 = mcd_raw_rsrc(TWO ? s2 : s1, N * C * Hi * Wi * 4);
-  const mcd_i32x4 rsl = mcd_raw_rsrc(labels != nullptr ? (const void*)labels : (const void*)s1, labels != nullptr ? N * Ho * Wo * 8 : 0);
-  const unsigned lds_s = (unsigned)(size_t)(__attribute__((address_space(3))) float*)sin0;
-  const unsigned lds_l = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lab0;
-  auto issue = [&](int item, int buf) {  // the inputs of one item -> LDS buffer `buf` (zeros outside the map)
-    const int seg = item % nseg, r = item / nseg;
-    const int iyg = r % (Hi + 1), n = r / (Hi + 1);
-    const int ixb = seg * (UP_COLS / 8) - 1;
-#pragma unroll
-    for (int k = 0; k < SPK; ++k) {
-      const int i = threadIdx.x + k * UP_NT;
-      const int b = i & 1, a = (i >> 1) & 1, q = i >> 2;
-      const int j = q % UP_JP, c = q / UP_JP;
-      const int iy = iyg - a, ix = ixb + j + 1 - b;
-      const bool ok = c < C && (unsigned)iy < (unsigned)Hi && (unsigned)ix < (unsigned)Wi;
-      const unsigned voff = ok ? (unsigned)((((n * C + c) * Hi + iy) * Wi + ix) * 4) : UP_OOB;
-      mcd_hidden_dma<4>(rs1, __builtin_amdgcn_readfirstlane(lds_s + 4u * ((buf * HEADS) * SP + k * UP_NT + ky0 * 64)), voff);
-      if (TWO) mcd_hidden_dma<4>(rs2, __builtin_amdgcn_readfirstlane(lds_s + 4u * ((buf * HEADS + 1) * SP + k * UP_NT + ky0 * 64)), voff);
-    }
-    if (labels != nullptr) {
-      const int oy = 8 * iyg - 4 + ky0;
-      const unsigned voff = (lane < 32 && (unsigned)oy < (unsigned)Ho) ? (unsigned)(((n * Ho + oy) * Wo + seg * UP_COLS + 2 * lane) * 8) : UP_OOB;
-      mcd_hidden_dma<16>(rsl, __builtin_amdgcn_readfirstlane(lds_l + 1024u * (buf * (UP_NT / 64) + ky0)), voff);
-    }
-  };
-  const int nst = (g1 != nullptr ? C : 0) + ((TWO && g2 != nullptr) ? C : 0);  // stores per wave and item
-  float ce1 = 0.f, ce2 = 0.f, dsum = 0.f;
-  int item = blockIdx.x, buf = 0;
-  int behind = 0;  // wave-uniform: the stores this wave issued after its last DMA
-  __syncthreads();  // (the kernels and class weights are staged before anybody's DMA could be mistaken for them -- and for the first barrier below)
-  if (item < items) issue(item, 0);
-  for (; item < items; item += gridDim.x, buf ^= 1) {
-    // this item's inputs have landed (issued before `behind` stores: in-order counter), every wave is done with the other buffer
-    if (__builtin_amdgcn_readfirstlane(behind) >= 63)
-      asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");  // (outside the branch: one barrier whatever the compiler makes of it)
-    if (item + (int)gridDim.x < items) issue(item + gridDim.x, buf ^ 1);
-    behind = 0;
-    const int seg = item % nseg, r = item / nseg;
-    const int iyg = r % (Hi + 1), n = r / (Hi + 1);
-    const int oy = 8 * iyg - 4 + ky0;
-    const int ox = seg * UP_COLS + lane;
-    if (oy >= 0 && oy < Ho) {  // wave-uniform
-      behind = nst;
-      if (ox < Wo) {
-        int Cv = C;
-        asm volatile("" : "+s"(Cv));
-        const int kx0 = (ox + 4) & 7;
-        const int jp = ((ox + 4) >> 3) - seg * (UP_COLS / 8);
-        int woff = (ky0 * 8 + kx0) * 4, soff = jp * 4 + buf * HEADS * SP;
-        asm volatile("" : "+v"(woff), "+v"(soff));
-        float a[NCMAX], b[NCMAX];
-#pragma unroll
-        for (int c0 = 0; c0 < NCMAX; c0 += 4) {
-          MCD_OPAQUE_TRUE(go);
-          if (go) {
-#pragma unroll
-            for (int c = c0; c < c0 + 4; ++c) {
-              if (c >= NCMAX) continue;
-              b[c] = -INFINITY;
-#pragma unroll
-              for (int h = 0; h < HEADS; ++h) {
-                const float4 wv = *reinterpret_cast<const float4*>(wl + woff + (h * NCMAX + c) * 256);
-                const float4 sv = *reinterpret_cast<const float4*>(sin0 + soff + h * SP + c * (UP_JP * 4));
-                float o = 0.f;
-                o = fmaf(sv.x, wv.x, o);
-                o = fmaf(sv.y, wv.y, o);
-                o = fmaf(sv.z, wv.z, o);
-                o = fmaf(sv.w, wv.w, o);
-                if (!EXACT && c >= Cv) o = -INFINITY;
-                if (h == 0)
-                  a[c] = o;
-                else
-                  b[c] = o;
-              }
-            }
-          }
-        }
-        const size_t HW = (size_t)Ho * Wo;
-        const size_t hw = (size_t)oy * Wo + ox;
-        int y = -1;
-        float wy = 0.f;
-        if (labels != nullptr) {
-          const int64_t yl = *reinterpret_cast<const int64_t*>(lab0 + (buf * (UP_NT / 64) + ky0) * 1024 + lane * 8);
-          if (yl != ignore_index && yl >= 0 && yl < C) {
-            y = (int)yl;
-            wy = cwl[y];
-          }
-        }
-        float e1 = 0.f, e2 = 0.f, ds = 0.f;
-        pixel_losses<NCMAX, TWO>(a, b, y, wy, ce_coef, diff_coef, losses_w, g1, g2, (size_t)n * C * HW + hw, HW, Cv, inv_m, e1, e2, ds);
-        ce1 += e1;
-        ce2 += e2;
-        dsum += ds;
-      }
-    }
-  }
-  __shared__ float sh[3][UP_NT / 64];
-  ce1 = wave_sum(ce1);
-  ce2 = wave_sum(ce2);
-  dsum = wave_sum(dsum);
-  if (lane == 0) {
-    sh[0][ky0] = ce1;
-    sh[1][ky0] = ce2;
-    sh[2][ky0] = dsum;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) {
-    const int q = threadIdx.x;
-    float t = 0.f;
-    for (int k = 0; k < UP_NT / 64; ++k) t += sh[q][k];
-    part[(size_t)blockIdx.x * 3 + q] = t;
-  }
-}
+// The kernels themselves (loss_front.h), twice: the L1 family, then the two-head distances.  A wave of the LDS-DMA kernel issues the
+// same 2 C gradient stores per item behind the next item's DMAs whatever the distance (pixel_dist stores where pixel_losses does), so
+// its counted wait holds for the new kernels as well (_lib.loss_dma_store_counts for the L1 names, _lib.dist_dma_store_counts for the new ones).
+#define MCD_FRONT_T2 template <int NCMAX, bool TWO>
+#define MCD_FRONT_T3 template <int NCMAX, bool TWO, bool EXACT>
+#define MCD_FRONT_PLAIN softmax_ce_l1_kernel
+#define MCD_FRONT_UP8 up8_softmax_ce_l1_kernel
+#define MCD_FRONT_DMA up8_softmax_ce_l1_dma_kernel
+#define MCD_FRONT_HEADS
+#define MCD_FRONT_PIXEL pixel_losses<NCMAX, TWO>
+#include "loss_front.h"
+#undef MCD_FRONT_T2
+#undef MCD_FRONT_T3
+#undef MCD_FRONT_PLAIN
+#undef MCD_FRONT_UP8
+#undef MCD_FRONT_DMA
+#undef MCD_FRONT_HEADS
+#undef MCD_FRONT_PIXEL
+
+#define MCD_FRONT_T2 template <int NCMAX, int KIND>
+#define MCD_FRONT_T3 template <int NCMAX, bool EXACT, int KIND>
+#define MCD_FRONT_PLAIN softmax_ce_dist_kernel
+#define MCD_FRONT_UP8 up8_softmax_ce_dist_kernel
+#define MCD_FRONT_DMA up8_softmax_ce_dist_dma_kernel
+#define MCD_FRONT_HEADS constexpr bool TWO = true
+#define MCD_FRONT_PIXEL pixel_dist<NCMAX, KIND>
+#include "loss_front.h"
+#undef MCD_FRONT_T2
+#undef MCD_FRONT_T3
+#undef MCD_FRONT_PLAIN
+#undef MCD_FRONT_UP8
+#undef MCD_FRONT_DMA
+#undef MCD_FRONT_HEADS
+#undef MCD_FRONT_PIXEL
 
 // has_ce: a cross-entropy term was requested.  With an all-background / all-ignored batch the normaliser W = sum w[y] is 0
 // and the reference's weighted mean is 0/0: nn.NLLLoss2d returns NaN and NaN gradients (loss.py:7-13).  The kernel does the
@@ -616,26 +443,34 @@ int wsum_blocks(int64_t P) {
 }
 
 template <int NCMAX>
-void launch_loss(bool two, dim3 grid, hipStream_t st, const float* z1, const float* z2, const int64_t* labels, const float* cw,
+void launch_loss(int kind, bool two, dim3 grid, hipStream_t st, const float* z1, const float* z2, const int64_t* labels, const float* cw,
                  int64_t ignore_index, float ce_coef, float diff_coef, const float* losses, float* g1, float* g2, float* part,
                  int C, int HW, int64_t P, float inv_m) {
-  if (two)
-    hipLaunchKernelGGL((softmax_ce_l1_kernel<NCMAX, true>), grid, dim3(LOSS_BLOCK), 0, st, z1, z2, labels, cw, ignore_index, ce_coef,
-                       diff_coef, losses, g1, g2, part, C, HW, P, inv_m);
-  else
-    hipLaunchKernelGGL((softmax_ce_l1_kernel<NCMAX, false>), grid, dim3(LOSS_BLOCK), 0, st, z1, z2, labels, cw, ignore_index,
-                       ce_coef, diff_coef, losses, g1, g2, part, C, HW, P, inv_m);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, dim3(LOSS_BLOCK), 0, st, z1, z2, labels, cw, ignore_index, ce_coef, diff_coef, losses, g1, g2, part, C,
+                       HW, P, inv_m);
+  };
+  switch (kind) {
+    case DIST_SYMKL: go(softmax_ce_dist_kernel<NCMAX, DIST_SYMKL>); break;
+    case DIST_MIS_SYMKL: go(softmax_ce_dist_kernel<NCMAX, DIST_MIS_SYMKL>); break;
+    case DIST_JSD: go(softmax_ce_dist_kernel<NCMAX, DIST_JSD>); break;
+    default:
+      if (two)
+        go(softmax_ce_l1_kernel<NCMAX, true>);
+      else
+        go(softmax_ce_l1_kernel<NCMAX, false>);
+  }
 }
 
 template <int NCMAX>
-int launch_up_loss(bool two, int blocks, size_t lds, hipStream_t st, const float* s1, const float* w1, const float* s2, const float* w2,
-                   const int64_t* labels, const float* cw, int64_t ignore_index, float ce_coef, float diff_coef, const float* losses,
-                   float* g1, float* g2, float* part, int N, int C, int Hi, int Wi, float inv_m) {
+int launch_up_loss(const char* entry, int kind, bool two, int blocks, size_t lds, hipStream_t st, const float* s1, const float* w1, const float* s2,
+                   const float* w2, const int64_t* labels, const float* cw, int64_t ignore_index, float ce_coef, float diff_coef,
+                   const float* losses, float* g1, float* g2, float* part, int N, int C, int Hi, int Wi, float inv_m) {
   auto go = [&](auto kern) {
     if (lds > 64 * 1024) {
       const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) {
-        mcdseg_set_error("up8_softmax_ce_l1: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+        mcdseg_set_error("%s: cannot reserve %zu bytes of LDS: %s", entry, lds, hipGetErrorString(e));
         return -5;
       }
     }
@@ -643,25 +478,36 @@ int launch_up_loss(bool two, int blocks, size_t lds, hipStream_t st, const float
                        g1, g2, part, N, C, Hi, Wi, inv_m);
     return 0;
   };
-  return two ? go(up8_softmax_ce_l1_kernel<NCMAX, true>) : go(up8_softmax_ce_l1_kernel<NCMAX, false>);
+  switch (kind) {
+    case DIST_SYMKL: return go(up8_softmax_ce_dist_kernel<NCMAX, DIST_SYMKL>);
+    case DIST_MIS_SYMKL: return go(up8_softmax_ce_dist_kernel<NCMAX, DIST_MIS_SYMKL>);
+    case DIST_JSD: return go(up8_softmax_ce_dist_kernel<NCMAX, DIST_JSD>);
+    default: return two ? go(up8_softmax_ce_l1_kernel<NCMAX, true>) : go(up8_softmax_ce_l1_kernel<NCMAX, false>);
+  }
 }
 
 template <int NCMAX, bool EXACT>
-int launch_up_loss_dma(bool two, int blocks, hipStream_t st, const float* s1, const float* w1, const float* s2, const float* w2,
+int launch_up_loss_dma(const char* entry, int kind, bool two, int blocks, hipStream_t st, const float* s1, const float* w1, const float* s2, const float* w2,
                        const int64_t* labels, const float* cw, int64_t ignore_index, float ce_coef, float diff_coef, const float* losses,
                        float* g1, float* g2, float* part, int N, int C, int Hi, int Wi, float inv_m) {
   auto go = [&](auto kern, size_t lds) {
     const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) {
-      mcdseg_set_error("up8_softmax_ce_l1: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e));
+      mcdseg_set_error("%s: cannot reserve %zu bytes of LDS: %s", entry, lds, hipGetErrorString(e));
       return -5;
     }
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(UP_NT), lds, st, s1, w1, s2, w2, labels, cw, ignore_index, ce_coef, diff_coef, losses,
                        g1, g2, part, N, C, Hi, Wi, inv_m);
     return 0;
   };
-  return two ? go(up8_softmax_ce_l1_dma_kernel<NCMAX, true, EXACT>, UpDmaLayout<NCMAX, true>::BYTES)
-             : go(up8_softmax_ce_l1_dma_kernel<NCMAX, false, EXACT>, UpDmaLayout<NCMAX, false>::BYTES);
+  switch (kind) {
+    case DIST_SYMKL: return go(up8_softmax_ce_dist_dma_kernel<NCMAX, EXACT, DIST_SYMKL>, UpDmaLayout<NCMAX, true>::BYTES);
+    case DIST_MIS_SYMKL: return go(up8_softmax_ce_dist_dma_kernel<NCMAX, EXACT, DIST_MIS_SYMKL>, UpDmaLayout<NCMAX, true>::BYTES);
+    case DIST_JSD: return go(up8_softmax_ce_dist_dma_kernel<NCMAX, EXACT, DIST_JSD>, UpDmaLayout<NCMAX, true>::BYTES);
+    default:
+      return two ? go(up8_softmax_ce_l1_dma_kernel<NCMAX, true, EXACT>, UpDmaLayout<NCMAX, true>::BYTES)
+                 : go(up8_softmax_ce_l1_dma_kernel<NCMAX, false, EXACT>, UpDmaLayout<NCMAX, false>::BYTES);
+  }
 }
 
 // the instantiation of the DMA kernel for C classes: the benchmark's 41 has its own (no padding classes: 15 % less arithmetic)
@@ -696,16 +542,17 @@ extern "C" int mcdseg_label_weight_sum(const int64_t* labels, const float* class
   return 0;
 }
 
-extern "C" int mcdseg_softmax_ce_l1(const float* z1, const float* z2, const int64_t* labels, const float* class_weight,
-                                    int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in, float* g1, float* g2,
-                                    float* losses, int32_t N, int32_t C, int32_t HW, void* workspace, size_t workspace_bytes,
-                                    void* stream) {
-  MCD_REQUIRE(z1 && losses && workspace, "softmax_ce_l1: null pointer");
-  MCD_REQUIRE(N > 0 && C > 0 && HW > 0, "softmax_ce_l1: bad dims");
-  MCD_REQUIRE(C <= 48, "softmax_ce_l1: at most 48 classes are kept in registers (got %d)", C);
-  MCD_REQUIRE(z2 != nullptr || (g2 == nullptr && diff_coef == 0.f), "softmax_ce_l1: discrepancy needs z2");
-  MCD_REQUIRE(labels != nullptr || ce_coef == 0.f, "softmax_ce_l1: cross-entropy needs labels");
-  MCD_REQUIRE(workspace_bytes >= mcdseg_loss_workspace_bytes(N, HW), "softmax_ce_l1: workspace too small");
+// both entry points of the plain-logit kernels; ``kind`` has been checked
+static int softmax_ce_any(const char* entry, int kind, const float* z1, const float* z2, const int64_t* labels, const float* class_weight,
+                          int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in, float* g1, float* g2, float* losses,
+                          int32_t N, int32_t C, int32_t HW, void* workspace, size_t workspace_bytes, void* stream) {
+  MCD_REQUIRE(z1 && losses && workspace, "%s: null pointer", entry);
+  MCD_REQUIRE(N > 0 && C > 0 && HW > 0, "%s: bad dims", entry);
+  MCD_REQUIRE(C <= 48, "%s: at most 48 classes are kept in registers (got %d)", entry, C);
+  MCD_REQUIRE(z2 != nullptr || (g2 == nullptr && diff_coef == 0.f), "%s: discrepancy needs z2", entry);
+  MCD_REQUIRE(z2 != nullptr || kind == DIST_L1, "%s: dist_kind %d is a distance between two heads: z2 is NULL", entry, kind);
+  MCD_REQUIRE(labels != nullptr || ce_coef == 0.f, "%s: cross-entropy needs labels", entry);
+  MCD_REQUIRE(workspace_bytes >= mcdseg_loss_workspace_bytes(N, HW), "%s: workspace too small", entry);
   const int64_t P = (int64_t)N * HW;
   const int64_t nblk = ceil_div64(P, LOSS_BLOCK);
   hipStream_t st = (hipStream_t)stream;
@@ -727,19 +574,37 @@ extern "C" int mcdseg_softmax_ce_l1(const float* z1, const float* z2, const int6
   dim3 grid((unsigned)nblk);
   const bool two = z2 != nullptr;
   if (C <= 16)
-    launch_loss<16>(two, grid, st, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2, part, C, HW, P,
+    launch_loss<16>(kind, two, grid, st, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2, part, C, HW, P,
                     (float)inv_m);
   else if (C <= 24)
-    launch_loss<24>(two, grid, st, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2, part, C, HW, P,
+    launch_loss<24>(kind, two, grid, st, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2, part, C, HW, P,
                     (float)inv_m);
   else
-    launch_loss<48>(two, grid, st, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2, part, C, HW, P,
+    launch_loss<48>(kind, two, grid, st, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2, part, C, HW, P,
                     (float)inv_m);
-  MCD_LAUNCH_CHECK("softmax_ce_l1");
+  MCD_LAUNCH_CHECK(entry);
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, nblk, losses, inv_m,
                      labels != nullptr ? 1 : 0);
   MCD_LAUNCH_CHECK("loss_finalize");
   return 0;
+}
+
+extern "C" int mcdseg_softmax_ce_l1(const float* z1, const float* z2, const int64_t* labels, const float* class_weight,
+                                    int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in, float* g1, float* g2,
+                                    float* losses, int32_t N, int32_t C, int32_t HW, void* workspace, size_t workspace_bytes,
+                                    void* stream) {
+  return softmax_ce_any("softmax_ce_l1", DIST_L1, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, wsum_in, g1, g2, losses, N, C, HW,
+                        workspace, workspace_bytes, stream);
+}
+
+extern "C" int mcdseg_softmax_ce_dist(const float* z1, const float* z2, const int64_t* labels, const float* class_weight,
+                                      int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in, float* g1, float* g2,
+                                      float* losses, int32_t N, int32_t C, int32_t HW, int32_t dist_kind, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  MCD_REQUIRE(dist_kind >= DIST_L1 && dist_kind <= DIST_JSD, "softmax_ce_dist: unknown dist_kind %d (MCDSEG_DIST_L1 .. MCDSEG_DIST_JSD)",
+              dist_kind);
+  return softmax_ce_any("softmax_ce_dist", dist_kind, z1, z2, labels, class_weight, ignore_index, ce_coef, diff_coef, wsum_in, g1, g2, losses, N, C, HW,
+                        workspace, workspace_bytes, stream);
 }
 
 // persistent workgroups: one per CU (the kernels of all classes fill most of a CU's LDS), never more than there are items
@@ -753,18 +618,19 @@ extern "C" size_t mcdseg_up8_loss_workspace_bytes(int32_t N, int32_t Hi, int32_t
   return (size_t)(up_loss_blocks(N, Hi, Wi) * 3 + wsum_blocks((int64_t)N * Hi * Wi * 64)) * sizeof(float);
 }
 
-extern "C" int mcdseg_up8_softmax_ce_l1(const float* s1, const float* w1, const float* s2, const float* w2, const int64_t* labels,
-                                        const float* class_weight, int64_t ignore_index, float ce_coef, float diff_coef,
-                                        const float* wsum_in, float* g1, float* g2, float* losses, int32_t N, int32_t C, int32_t Hi,
-                                        int32_t Wi, void* workspace, size_t workspace_bytes, void* stream) {
-  MCD_REQUIRE(s1 && w1 && losses && workspace, "up8_softmax_ce_l1: null pointer");
-  MCD_REQUIRE(N > 0 && C > 0 && Hi > 0 && Wi > 0, "up8_softmax_ce_l1: bad dims");
-  MCD_REQUIRE(C <= 48, "up8_softmax_ce_l1: at most 48 classes are kept in registers (got %d)", C);
-  MCD_REQUIRE((s2 == nullptr) == (w2 == nullptr), "up8_softmax_ce_l1: s2 and w2 come together");
-  MCD_REQUIRE(s2 != nullptr || (g2 == nullptr && diff_coef == 0.f), "up8_softmax_ce_l1: discrepancy needs the second head");
-  MCD_REQUIRE(labels != nullptr || ce_coef == 0.f, "up8_softmax_ce_l1: cross-entropy needs labels");
-  MCD_REQUIRE((int64_t)N * (Hi + 1) * ceil_div(8 * Wi, UP_COLS) < (1ll << 31), "up8_softmax_ce_l1: too many patches");
-  MCD_REQUIRE(workspace_bytes >= mcdseg_up8_loss_workspace_bytes(N, Hi, Wi), "up8_softmax_ce_l1: workspace too small");
+static int up8_softmax_ce_any(const char* entry, int kind, const float* s1, const float* w1, const float* s2, const float* w2, const int64_t* labels,
+                              const float* class_weight, int64_t ignore_index, float ce_coef, float diff_coef, const float* wsum_in,
+                              float* g1, float* g2, float* losses, int32_t N, int32_t C, int32_t Hi, int32_t Wi, void* workspace,
+                              size_t workspace_bytes, void* stream) {
+  MCD_REQUIRE(s1 && w1 && losses && workspace, "%s: null pointer", entry);
+  MCD_REQUIRE(N > 0 && C > 0 && Hi > 0 && Wi > 0, "%s: bad dims", entry);
+  MCD_REQUIRE(C <= 48, "%s: at most 48 classes are kept in registers (got %d)", entry, C);
+  MCD_REQUIRE((s2 == nullptr) == (w2 == nullptr), "%s: s2 and w2 come together", entry);
+  MCD_REQUIRE(s2 != nullptr || (g2 == nullptr && diff_coef == 0.f), "%s: discrepancy needs the second head", entry);
+  MCD_REQUIRE(s2 != nullptr || kind == DIST_L1, "%s: dist_kind %d is a distance between two heads: s2 is NULL", entry, kind);
+  MCD_REQUIRE(labels != nullptr || ce_coef == 0.f, "%s: cross-entropy needs labels", entry);
+  MCD_REQUIRE((int64_t)N * (Hi + 1) * ceil_div(8 * Wi, UP_COLS) < (1ll << 31), "%s: too many patches", entry);
+  MCD_REQUIRE(workspace_bytes >= mcdseg_up8_loss_workspace_bytes(N, Hi, Wi), "%s: workspace too small", entry);
   const int64_t P = (int64_t)N * Hi * Wi * 64;
   const int nblk = up_loss_blocks(N, Hi, Wi);
   hipStream_t st = (hipStream_t)stream;
@@ -786,20 +652,20 @@ extern "C" int mcdseg_up8_softmax_ce_l1(const float* s1, const float* w1, const 
   if (up_loss_dma_ok(N, C, Hi, Wi, labels != nullptr)) {
     int rc;
 #define MCD_UP_DMA(NC)                                                                                                              \
-  rc = (C == NC) ? launch_up_loss_dma<NC, true>(two, nblk, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, \
+  rc = (C == NC) ? launch_up_loss_dma<NC, true>(entry, kind, two, nblk, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, \
                                                 losses, g1, g2, part, N, C, Hi, Wi, (float)inv_m)                                    \
-                 : launch_up_loss_dma<NC, false>(two, nblk, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef,         \
+                 : launch_up_loss_dma<NC, false>(entry, kind, two, nblk, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef,         \
                                                  diff_coef, losses, g1, g2, part, N, C, Hi, Wi, (float)inv_m)
     switch (up_loss_dma_ncmax(C)) {
       case 16: MCD_UP_DMA(16); break;
       case 24: MCD_UP_DMA(24); break;
-      case 41: rc = launch_up_loss_dma<41, true>(two, nblk, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef,
+      case 41: rc = launch_up_loss_dma<41, true>(entry, kind, two, nblk, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef,
                                                  losses, g1, g2, part, N, C, Hi, Wi, (float)inv_m); break;
       default: MCD_UP_DMA(48); break;
     }
 #undef MCD_UP_DMA
     if (rc != 0) return rc;
-    MCD_LAUNCH_CHECK("up8_softmax_ce_l1 (dma)");
+    MCD_LAUNCH_CHECK(entry);
     hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int64_t)nblk, losses, inv_m,
                        labels != nullptr ? 1 : 0);
     MCD_LAUNCH_CHECK("loss_finalize");
@@ -809,20 +675,38 @@ extern "C" int mcdseg_up8_softmax_ce_l1(const float* s1, const float* w1, const 
   const size_t lds = (size_t)(two ? 2 : 1) * ncmax * (256 + 4 * UP_JP) * sizeof(float);
   int rc;
   if (C <= 16)
-    rc = launch_up_loss<16>(two, nblk, lds, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2,
+    rc = launch_up_loss<16>(entry, kind, two, nblk, lds, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2,
                             part, N, C, Hi, Wi, (float)inv_m);
   else if (C <= 24)
-    rc = launch_up_loss<24>(two, nblk, lds, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2,
+    rc = launch_up_loss<24>(entry, kind, two, nblk, lds, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2,
                             part, N, C, Hi, Wi, (float)inv_m);
   else
-    rc = launch_up_loss<48>(two, nblk, lds, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2,
+    rc = launch_up_loss<48>(entry, kind, two, nblk, lds, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, losses, g1, g2,
                             part, N, C, Hi, Wi, (float)inv_m);
   if (rc != 0) return rc;
-  MCD_LAUNCH_CHECK("up8_softmax_ce_l1");
+  MCD_LAUNCH_CHECK(entry);
   hipLaunchKernelGGL(loss_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int64_t)nblk, losses, inv_m,
                      labels != nullptr ? 1 : 0);
   MCD_LAUNCH_CHECK("loss_finalize");
   return 0;
+}
+
+extern "C" int mcdseg_up8_softmax_ce_l1(const float* s1, const float* w1, const float* s2, const float* w2, const int64_t* labels,
+                                        const float* class_weight, int64_t ignore_index, float ce_coef, float diff_coef,
+                                        const float* wsum_in, float* g1, float* g2, float* losses, int32_t N, int32_t C, int32_t Hi,
+                                        int32_t Wi, void* workspace, size_t workspace_bytes, void* stream) {
+  return up8_softmax_ce_any("up8_softmax_ce_l1", DIST_L1, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, wsum_in, g1, g2, losses, N,
+                            C, Hi, Wi, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mcdseg_up8_softmax_ce_dist(const float* s1, const float* w1, const float* s2, const float* w2, const int64_t* labels,
+                                          const float* class_weight, int64_t ignore_index, float ce_coef, float diff_coef,
+                                          const float* wsum_in, float* g1, float* g2, float* losses, int32_t N, int32_t C, int32_t Hi,
+                                          int32_t Wi, int32_t dist_kind, void* workspace, size_t workspace_bytes, void* stream) {
+  MCD_REQUIRE(dist_kind >= DIST_L1 && dist_kind <= DIST_JSD,
+              "up8_softmax_ce_dist: unknown dist_kind %d (MCDSEG_DIST_L1 .. MCDSEG_DIST_JSD)", dist_kind);
+  return up8_softmax_ce_any("up8_softmax_ce_dist", dist_kind, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, wsum_in, g1, g2, losses, N,
+                            C, Hi, Wi, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mcdseg_predict_workspace_bytes(int32_t N, int32_t HW) {

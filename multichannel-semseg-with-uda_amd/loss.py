@@ -5,12 +5,13 @@
   Diff2d                       loss.py:93-100  mean |softmax(o1) - softmax(o2)|
   get_prob_distance_criterion  loss.py:192-210 ("diff" is the default ``--d_loss``, argmyparse.py:131)
 
-Both criteria are thin ``nn.Module`` shells over ``mcdseg.ops`` (forward value and d/dlogits come out of
+All criteria are thin ``nn.Module`` shells over ``mcdseg.ops`` (forward value and d/dlogits come out of
 one streaming pass).  ``DiscrepancyLoss`` is an alias of ``Diff2d`` (BASELINE.json uses that name; the
 reference has no such symbol).  The other distances of the reference (JSD, Symkl2d, MySymkl2d, SpatialJSD2d,
-MisSymKLD; loss.py:70-189) are off the hot path: they are kept as plain-torch criteria over the logits the HIP
-classifiers produce, so ``adapt_trainer.py --d_loss symkl`` keeps working through the
-drop-in statement loop; only 'diff' runs on the fused kernel.
+MisSymKLD; loss.py:70-189) are three functions of the two softmaxes; each class names
+its function in ``dist_kind`` (``mcdseg.ops.DIST_KINDS``) and runs ``ops.prob_distance`` -- the fused HIP
+kernel -- on fp32 GPU logits.  Anything else (CPU tensors, fp64, ``size_average=False``) evaluates the torch
+expression the class carries, which is also the statement of what the kernel computes.
 """
 import torch
 import torch.nn as nn
@@ -62,6 +63,8 @@ class ProbCrossEntropyLoss2d(nn.Module):
 
 
 class Diff2d(nn.Module):
+    dist_kind = 0
+
     def __init__(self, weight=None, size_average=True):
         super().__init__()
         self.weight = weight
@@ -73,20 +76,30 @@ class Diff2d(nn.Module):
 DiscrepancyLoss = Diff2d
 
 
-# ---- the non-default probability distances (plain torch; torch 0.4's implicit softmax dim of a 4-D tensor is 1, and
+# ---- the non-default probability distances (torch 0.4's implicit softmax dim of a 4-D tensor is 1, and
 # F.kl_div(input, target, size_average=True) is the element-wise mean of target * (log(target) - input))
 def _kl_mean(log_q, p, size_average=True):
     return F.kl_div(log_q, p, reduction="mean" if size_average else "sum")
 
 
+def _on_kernel(inputs1, inputs2, size_average=True):
+    """the HIP kernel takes this call: element mean, two fp32 GPU tensors of one 4-D shape with at most the 48 classes it keeps in registers"""
+    return (size_average and inputs1.is_cuda and inputs2.is_cuda and inputs1.dtype == inputs2.dtype == torch.float32
+            and inputs1.dim() == 4 and inputs1.shape == inputs2.shape and inputs1.shape[1] <= 48)
+
+
 class JSD(nn.Module):
     """loss.py:78-89: 0.5 * (KL(p1 || softmax(m)) + KL(p2 || softmax(m))) with m the mean of the LOGITS"""
+
+    dist_kind = 3  # mcdseg.ops.DIST_KINDS / MCDSEG_DIST_* of include/mcdseg.h
 
     def __init__(self, weight=None, size_average=True):
         super().__init__()
         self.weight, self.size_average = weight, size_average
 
     def forward(self, inputs1, inputs2):
+        if _on_kernel(inputs1, inputs2, self.size_average):
+            return ops.prob_distance(inputs1, inputs2, self.dist_kind)
         log_m = F.log_softmax(0.5 * (inputs1 + inputs2), dim=1)
         return 0.5 * (_kl_mean(log_m, F.softmax(inputs1, dim=1), self.size_average) +
                       _kl_mean(log_m, F.softmax(inputs2, dim=1), self.size_average))
@@ -95,11 +108,15 @@ class JSD(nn.Module):
 class Symkl2d(nn.Module):
     """loss.py:103-118: symmetric KL over rows of ``n_target_ch`` entries (a plain ``view`` of NCHW, as the reference does)"""
 
+    dist_kind = 1  # mcdseg.ops.DIST_KINDS / MCDSEG_DIST_* of include/mcdseg.h
+
     def __init__(self, weight=None, n_target_ch=None, size_average=True):
         super().__init__()
         self.weight, self.n_target_ch, self.size_average = weight, n_target_ch, size_average
 
     def forward(self, inputs1, inputs2):
+        if _on_kernel(inputs1, inputs2, self.size_average):
+            return ops.prob_distance(inputs1, inputs2, self.dist_kind)
         rows = lambda t: t.reshape(-1, self.n_target_ch)  # noqa: E731
         p1, p2 = rows(F.softmax(inputs1, dim=1)), rows(F.softmax(inputs2, dim=1))
         l1, l2 = rows(F.log_softmax(inputs1, dim=1)), rows(F.log_softmax(inputs2, dim=1))
@@ -109,11 +126,15 @@ class Symkl2d(nn.Module):
 class MySymkl2d(nn.Module):
     """loss.py:144-154: mean over all elements of 0.5 * (p1 log(p1/p2) + p2 log(p2/p1))"""
 
+    dist_kind = 1  # mcdseg.ops.DIST_KINDS / MCDSEG_DIST_* of include/mcdseg.h
+
     def __init__(self, weight=None, size_average=True):
         super().__init__()
         self.weight = weight
 
     def forward(self, inputs1, inputs2):
+        if _on_kernel(inputs1, inputs2):
+            return ops.prob_distance(inputs1, inputs2, self.dist_kind)
         p1, p2 = F.softmax(inputs1, dim=1), F.softmax(inputs2, dim=1)
         return torch.mean(0.5 * (p1 * torch.log(p1 / p2) + p2 * torch.log(p2 / p1)))
 
@@ -122,11 +143,15 @@ class MisSymKLD(nn.Module):
     """loss.py:66-75 (and SpatialJSD2d, loss.py:157-173, which evaluates the same expression): kl_div is handed
     PROBABILITIES where it expects log-probabilities -- 'strange but somehow works well' in the reference's words"""
 
+    dist_kind = 2  # mcdseg.ops.DIST_KINDS / MCDSEG_DIST_* of include/mcdseg.h
+
     def __init__(self, weight=None, size_average=True):
         super().__init__()
         self.weight = weight
 
     def forward(self, inputs1, inputs2):
+        if _on_kernel(inputs1, inputs2):
+            return ops.prob_distance(inputs1, inputs2, self.dist_kind)
         p1, p2 = F.softmax(inputs1, dim=1), F.softmax(inputs2, dim=1)
         return 0.5 * (_kl_mean(p1, p2) + _kl_mean(p2, p1))
 
@@ -135,7 +160,7 @@ SpatialJSD2d = MisSymKLD
 
 
 def get_prob_distance_criterion(criterion_name, n_class=None):
-    """loss.py:192-210; 'diff' is the fused HIP kernel, the rest are the torch criteria above"""
+    """loss.py:192-210; every name runs on the fused HIP kernels (``dist_kind`` of the class says which distance)"""
     if criterion_name == "diff":
         return Diff2d()
     if criterion_name == "jsd":

@@ -101,6 +101,10 @@ _SIGNATURES = {
     "mcdseg_up8_loss_workspace_bytes": (c_size_t, [c_i32] * 3),
     "mcdseg_up8_softmax_ce_l1": (c_int, [c_void_p] * 6 + [c_i64, c_float, c_float] + [c_void_p] * 4 + [c_i32] * 4 +
                                  [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_softmax_ce_dist": (c_int, [c_void_p] * 4 + [c_i64, c_float, c_float] + [c_void_p] * 4 + [c_i32] * 4 +
+                               [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_up8_softmax_ce_dist": (c_int, [c_void_p] * 6 + [c_i64, c_float, c_float] + [c_void_p] * 4 + [c_i32] * 5 +
+                                   [c_void_p, c_size_t, c_void_p]),
     "mcdseg_label_weight_sum_workspace_bytes": (c_size_t, [c_i64]),
     "mcdseg_label_weight_sum": (c_int, [c_void_p, c_void_p, c_i64, c_i32, c_i64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "mcdseg_bilinear8_fwd": (c_int, [c_void_p, c_void_p] + [c_i32] * 4 + [c_void_p]),
@@ -280,7 +284,7 @@ def spills_inside_matrix_loops(path=None, prefix=("conv_gemm_split_pp_kernel", "
     return out
 
 
-def drains_inside_store_loops(path=None, prefix=("up8_softmax_ce_l1_dma_kernel", "up8_bwd_band_kernel")):
+def drains_inside_store_loops(path=None, prefix=("up8_softmax_ce_l1_dma_kernel", "up8_softmax_ce_dist_dma_kernel", "up8_bwd_band_kernel")):
     """[(kernel symbol, instruction)] of every ``s_waitcnt vmcnt(0)`` of these kernels that lies between an LDS-DMA issue and the last
     global store behind it; must be empty.  gfx950 counts loads, stores and LDS-DMA in ONE in-order counter: a ``vmcnt(0)`` there -- the
     compiler puts one in front of any load it tracks whose first use is inside the loop, and in front of LDS reads behind an LDS-DMA issued
@@ -326,7 +330,8 @@ def _kernel_bodies(path=None):
     return out
 
 
-HIDDEN_DMA_KERNELS = ("up8_softmax_ce_l1_dma_kernel", "up8_bwd_band_kernel", "conv_wgrad_split_tr64_kernel")  # users of mcd_hidden_dma
+HIDDEN_DMA_KERNELS = ("up8_softmax_ce_l1_dma_kernel", "up8_softmax_ce_dist_dma_kernel", "up8_bwd_band_kernel",
+                      "conv_wgrad_split_tr64_kernel")  # users of mcd_hidden_dma
 
 
 def hidden_dma_hazards(path=None):
@@ -368,6 +373,20 @@ def loss_dma_store_counts(path=None):
         if m:
             n = sum(1 for ln in body if re.search(r"\bglobal_store_dword\b", ln))
             key = (int(m.group(1)), 2 if m.group(2) == "1" else 1)
+            out[key] = min(n, out.get(key, n))
+    return out
+
+
+def dist_dma_store_counts(path=None):
+    """{(classes, distance kind): global stores} of the LDS-DMA kernels of the other probability distances
+    (``up8_softmax_ce_dist_dma_kernel<NC, EXACT, KIND>``, two heads always): the same contract as ``loss_dma_store_counts``"""
+    import re
+    out = {}
+    for sym, body in _kernel_bodies(path):
+        m = re.search(r"up8_softmax_ce_dist_dma_kernelILi(\d+)ELb[01]ELi(\d+)E", sym)
+        if m:
+            n = sum(1 for ln in body if re.search(r"\bglobal_store_dword\b", ln))
+            key = (int(m.group(1)), int(m.group(2)))
             out[key] = min(n, out.get(key, n))
     return out
 

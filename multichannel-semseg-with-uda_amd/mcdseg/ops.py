@@ -10,6 +10,7 @@ mirror the ATen call sites of the reference's hot path:
   cross_entropy2d  log_softmax + weighted NLL                       loss.py:7-13
   diff2d           mean |softmax - softmax|                         loss.py:93-100
   mcd_losses       both of the above in one fused kernel            adapt_trainer.py:163-212
+  prob_distance    the other distances of --d_loss (jsd, symkl, ...) loss.py:66-189
 """
 import collections
 import contextlib
@@ -1796,9 +1797,27 @@ def ce_normaliser(labels, class_weight, n_class, ignore_index=-100):
     return w / mdist.world_size()
 
 
-def mcd_losses(z1, z2, labels, class_weight, ignore_index=-100, ce_coef=0.0, diff_coef=0.0, want_grad=True, wsum=None):
+# The classifier discrepancies of --d_loss (loss.py:192-210) as the library's distance kinds (include/mcdseg.h MCDSEG_DIST_*): seven names,
+# four functions -- Symkl2d's rows and MySymkl2d's ratio are one expression under the element mean, and SpatialJSD2d evaluates MisSymKLD's.
+DIST_KINDS = {"diff": 0, "symkl": 1, "nmlsymkl": 1, "mysymkl": 1, "mis_symkl": 2, "spatial_jsd": 2, "jsd": 3}
+
+
+def dist_kind(dist):
+    """the library's kind (0..3) of a ``--d_loss`` name or of a kind; anything else is a ValueError (before the library is touched)"""
+    if isinstance(dist, str) and dist in DIST_KINDS:
+        return DIST_KINDS[dist]
+    if isinstance(dist, int) and not isinstance(dist, bool) and 0 <= dist <= 3:
+        return dist
+    raise ValueError("mcdseg: unknown probability distance %r (one of %s, or a kind 0..3)" % (dist, ", ".join(sorted(DIST_KINDS))))
+
+
+def mcd_losses(z1, z2, labels, class_weight, ignore_index=-100, ce_coef=0.0, diff_coef=0.0, want_grad=True, wsum=None, dist="diff"):
     """One fused pass.  Returns (losses[4] = CE1, CE2, Diff, sum w[y]; g1; g2) where
-    g_k = ce_coef * dCE_k/dz_k + diff_coef * dDiff/dz_k (None when not requested)."""
+    g_k = ce_coef * dCE_k/dz_k + diff_coef * dDiff/dz_k (None when not requested).  ``dist``: the discrepancy, a ``--d_loss`` name or a
+    kind of ``DIST_KINDS`` (anything but "diff" needs both heads)."""
+    kind = dist_kind(dist)
+    if kind != 0 and z2 is None:
+        raise ValueError("mcdseg: the distance %r is taken between two heads" % (dist,))
     L = lib()
     z1 = _req(z1, "logits")
     z2 = _req(z2, "logits")
@@ -1821,6 +1840,12 @@ def mcd_losses(z1, z2, labels, class_weight, ignore_index=-100, ce_coef=0.0, dif
     ws = _ws(L.mcdseg_loss_workspace_bytes(n, h * w), z1.device)
     nz = (1 if z2 is None else 2) * n * c * h * w
     byts = 4 * nz * (2 if want_grad else 1) + (8 * n * h * w if labels is not None else 0)
+    if kind != 0:
+        with _timed("softmax_ce_dist_kernel", (0, byts)):
+            check(L.mcdseg_softmax_ce_dist(_p(z1), _p(z2), _p(labels), _p(class_weight), int(ignore_index), float(ce_coef),
+                                           float(diff_coef), _p(wsum), _p(g1), _p(g2), _p(losses), n, c, h * w, kind, _p(ws),
+                                           ctypes.c_size_t(ws.numel() * 4), _stream()), "softmax_ce_dist")
+        return losses, g1, g2
     with _timed("softmax_ce_l1_kernel<48, %s>" % ("true" if z2 is not None else "false") if c > 24 else "softmax_ce_l1_kernel", (0, byts)):
         check(L.mcdseg_softmax_ce_l1(_p(z1), _p(z2), _p(labels), _p(class_weight), int(ignore_index), float(ce_coef),
                                      float(diff_coef), _p(wsum), _p(g1), _p(g2), _p(losses), n, c, h * w, _p(ws),
@@ -1828,21 +1853,30 @@ def mcd_losses(z1, z2, labels, class_weight, ignore_index=-100, ce_coef=0.0, dif
     return losses, g1, g2
 
 
-def up8_loss_kernel_name(n, c, hi, wi, two, labelled):
+def up8_loss_kernel_name(n, c, hi, wi, two, labelled, dist="diff"):
     """The kernel ``mcdseg_up8_softmax_ce_l1`` launches for this problem, as rocprofv3 prints it -- from the library's own dispatch
     (``mcdseg_up8_loss_variant``: the LDS-DMA kernel unless the option UP8_LOSS_DMA is 0 or a tensor outgrows a 32-bit buffer resource;
     the benchmark's 41 classes have an instantiation of their own)."""
+    kind = dist_kind(dist)
     two = "true" if two else "false"
     v = lib().mcdseg_up8_loss_variant(int(n), int(c), int(hi), int(wi), int(bool(labelled)))
+    if kind != 0:  # ``mcdseg_up8_softmax_ce_dist``: the same dispatch, kernels of their own (two heads always)
+        if v > 0:
+            return "up8_softmax_ce_dist_dma_kernel<%d, %s, %d>" % (v, "true" if c == v else "false", kind)
+        return "up8_softmax_ce_dist_kernel<%d, %d>" % (-v, kind)
     if v > 0:
         return "up8_softmax_ce_l1_dma_kernel<%d, %s, %s>" % (v, two, "true" if c == v else "false")
     return "up8_softmax_ce_l1_kernel<%d, %s>" % (-v, two)
 
 
-def up8_mcd_losses(s1, w1, s2, w2, labels, class_weight, ignore_index=-100, ce_coef=0.0, diff_coef=0.0, want_grad=True, wsum=None):
+def up8_mcd_losses(s1, w1, s2, w2, labels, class_weight, ignore_index=-100, ce_coef=0.0, diff_coef=0.0, want_grad=True, wsum=None,
+                   dist="diff"):
     """``mcd_losses(up8(s1, w1), up8(s2, w2), ...)`` without the full-resolution logits: the kernel forms each pixel's logits
     from the score maps [N,C,Hi,Wi] on the fly.  Returns (losses[4], g1, g2) with g_k [N,C,8Hi,8Wi] = the gradient w.r.t.
     the (never stored) logits of head k -- what ``_up8_bwd_input`` / ``_up8_bwd_weight`` consume."""
+    kind = dist_kind(dist)
+    if kind != 0 and s2 is None:
+        raise ValueError("mcdseg: the distance %r is taken between two heads" % (dist,))
     L = lib()
     s1, w1, s2, w2 = _req(s1, "scores"), _req(w1, "up8 weight"), _req(s2, "scores"), _req(w2, "up8 weight")
     _check_up(s1, w1)
@@ -1868,6 +1902,12 @@ def up8_mcd_losses(s1, w1, s2, w2, labels, class_weight, ignore_index=-100, ce_c
     ws = _ws(L.mcdseg_up8_loss_workspace_bytes(n, hi, wi), s1.device)
     heads = 1 if s2 is None else 2
     byts = 4 * heads * n * c * h * w * (1 if want_grad else 0) + 4 * heads * n * c * hi * wi + (8 * n * h * w if labels is not None else 0)
+    if kind != 0:
+        with _timed(up8_loss_kernel_name(n, c, hi, wi, True, labels is not None, kind), (0, byts)):
+            check(L.mcdseg_up8_softmax_ce_dist(_p(s1), _p(w1), _p(s2), _p(w2), _p(labels), _p(class_weight), int(ignore_index),
+                                               float(ce_coef), float(diff_coef), _p(wsum), _p(g1), _p(g2), _p(losses), n, c, hi, wi, kind,
+                                               _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()), "up8_softmax_ce_dist")
+        return losses, g1, g2
     with _timed(up8_loss_kernel_name(n, c, hi, wi, s2 is not None, labels is not None), (0, byts)):
         check(L.mcdseg_up8_softmax_ce_l1(_p(s1), _p(w1), _p(s2), _p(w2), _p(labels), _p(class_weight), int(ignore_index),
                                          float(ce_coef), float(diff_coef), _p(wsum), _p(g1), _p(g2), _p(losses), n, c, hi, wi,
@@ -2122,12 +2162,37 @@ class _Diff2d(torch.autograd.Function):
         return _scale_(g1, s), _scale_(g2, s)
 
 
+class _ProbDistance(torch.autograd.Function):
+    """a distance of ``DIST_KINDS`` between softmax(z1) and softmax(z2): value and both logit gradients from one kernel launch"""
+
+    @staticmethod
+    def forward(ctx, z1, z2, kind):
+        need = ctx.needs_input_grad[0] or ctx.needs_input_grad[1]
+        losses, g1, g2 = mcd_losses(z1, z2, None, None, diff_coef=1.0, want_grad=need, dist=kind)
+        ctx.g = (g1, g2)
+        return losses[2].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (g1, g2), ctx.g = ctx.g, None
+        s = _req(grad_out.reshape(1), "grad_output")
+        return _scale_(g1, s), _scale_(g2, s), None
+
+
 def cross_entropy2d(z, labels, class_weight=None, ignore_index=-100, size_average=True):
     return _CrossEntropy2d.apply(z, labels, class_weight, ignore_index, size_average)
 
 
 def diff2d(z1, z2):
     return _Diff2d.apply(z1, z2)
+
+
+def prob_distance(z1, z2, kind):
+    """``--d_loss`` distance ``kind`` (a name or a kind of ``DIST_KINDS``) between the two heads' logits [N,C,H,W], differentiable"""
+    kind = dist_kind(kind)
+    if kind == 0:
+        return _Diff2d.apply(z1, z2)
+    return _ProbDistance.apply(z1, z2, kind)
 
 
 # ------------------------------------------------------------------------------------------------ optimizer kernel

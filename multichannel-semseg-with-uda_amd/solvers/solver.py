@@ -8,6 +8,9 @@ written inline in each trainer.  ``MCDSolver.step`` follows ``adapt_trainer.py:1
   B  F1, F2    <- min  CE1 + CE2 (source)  -  Diff(F1(G(xt)), F2(G(xt)))
   C  G         <- min  Diff(target) * num_multiply_d_loss          (num_k times)
 
+``Diff`` is the criterion of ``--d_loss``: the L1 distance by default, or any other of ``loss.get_prob_distance_criterion`` -- the loss
+kernels compute each of them (``mcdseg.ops.DIST_KINDS``), so nothing below depends on which one it is.
+
 Differences from running the same statements through the drop-in modules -- none of them changes a
 result:
   * each phase evaluates its loss terms and both logit gradients with ONE fused kernel launch
@@ -120,8 +123,12 @@ class MCDSolver:
         # the gated MFNet fusions emit probabilities and are trained with ProbCrossEntropyLoss2d (adapt_mfnet_trainer.py:149):
         # that criterion runs as its own kernel per head; everything else takes the fused CE/CE kernel
         self.prob_criterion = criterion if type(criterion).__name__ == "ProbCrossEntropyLoss2d" else None
-        if type(criterion_d).__name__ != "Diff2d":
-            raise NotImplementedError("the fused solver implements d_loss='diff' (loss.py:93-100)")
+        # the discrepancy: any criterion of loss.get_prob_distance_criterion -- each names its distance in ``dist_kind``, and a criterion
+        # that asks for anything but the element mean (Symkl2d / JSD with size_average=False) is not what the kernels compute
+        self.dist = getattr(criterion_d, "dist_kind", None)
+        if self.dist not in set(ops.DIST_KINDS.values()) or not getattr(criterion_d, "size_average", True):
+            raise NotImplementedError("the fused solver implements the distances of loss.get_prob_distance_criterion (loss.py:192-210), "
+                                      "got %r" % (criterion_d,))
         self.num_k = num_k
         self.mult = float(num_multiply_d_loss)
         # step B's target forward doubles as step C's first (see the module docstring) -- for generator classes known to be repeatable
@@ -137,11 +144,14 @@ class MCDSolver:
 
     def _loss_backward(self, feats, labels, ce_coef=0.0, diff_coef=0.0):
         """Heads + loss + backward down to ``feats`` (and into the classifiers' parameters); returns losses[4]."""
+        # (a pass without a discrepancy term -- step A, step B's source half -- takes the L1 kernels whatever the distance: nobody reads
+        # losses[2] there, the cross-entropy values and gradients are bitwise the same, and the other distances cost more per launch)
+        dist = self.dist if diff_coef != 0.0 else 0
         if self.fused_up and len(feats) == 1:
             s = feats[0]
             w1, w2 = self.f1.up.weight, self.f2.up.weight
             losses, g1, g2 = ops.up8_mcd_losses(s, w1, s, w2, labels, self.class_weight, self.ignore_index, ce_coef=ce_coef,
-                                                diff_coef=diff_coef)
+                                                diff_coef=diff_coef, dist=dist)
             sd = s.detach()
             ds = None
             for w, g in ((w1, g1), (w2, g2)):
@@ -157,7 +167,7 @@ class MCDSolver:
         if labels is not None:
             losses, g1, g2 = self._ce(o1, o2, labels)
         else:
-            losses, g1, g2 = ops.mcd_losses(o1, o2, None, None, diff_coef=diff_coef)
+            losses, g1, g2 = ops.mcd_losses(o1, o2, None, None, diff_coef=diff_coef, dist=dist)
         torch.autograd.backward([o1, o2], [g1, g2])
         return losses
 

@@ -152,7 +152,7 @@ def simple_worker(a):
         def run():
             out = {}
             for tag, ce, df, lab in (("A", 1.0, 0.0, lbl), ("B", 1.0, -1.0, lbl), ("C", 0.0, 1.0, None)):  # the three forms of an MCD step
-                losses, g1, g2 = ops.up8_mcd_losses(s1, w1, s2, w2, lab, cw if lab is not None else None, ce_coef=ce, diff_coef=df)
+                losses, g1, g2 = ops.up8_mcd_losses(s1, w1, s2, w2, lab, cw if lab is not None else None, ce_coef=ce, diff_coef=df, dist=a.dist)
                 out.update({tag + ".losses": losses, tag + ".g1": g1, tag + ".g2": g2})
             return out
     elif a.op == "up8_bwd":
@@ -223,6 +223,7 @@ def main():
                     help="conv (default): two fused conv+BN+ReLU groups with their BatchNorm-backward intermediates; loss / up8_bwd: the kernels "
                          "with hand-counted waits around hidden LDS-DMAs, shape = N,C,Hi,Wi of the score maps (benchmark: 16,41,60,80); half: a "
                          "Bottleneck block of the 2-byte chain, shape = N,C,H,W")
+    ap.add_argument("--dist", default="diff", help="--op loss: the classifier discrepancy (a --d_loss name), i.e. which family of loss kernels")
     ap.add_argument("--procs", type=int, default=1)
     ap.add_argument("--iters", type=int, default=200)
     ap.add_argument("--shape", default="4,256,24,32")
@@ -233,7 +234,7 @@ def main():
     if a.worker or a.procs == 1:
         sys.exit(worker(a) if a.op == "conv" else simple_worker(a))
     cmd = [sys.executable, os.path.abspath(__file__), "--worker", "--op", a.op, "--iters", str(a.iters), "--shape", a.shape, "--dil", str(a.dil),
-           "--side_lag", str(a.side_lag)]
+           "--side_lag", str(a.side_lag), "--dist", a.dist]
     ps = [subprocess.Popen(cmd) for _ in range(a.procs)]
     rc = 0
     for p in ps:
