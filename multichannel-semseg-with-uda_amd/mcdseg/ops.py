@@ -17,6 +17,7 @@ import contextlib
 import ctypes
 import os
 import threading
+import types
 import weakref
 
 import torch
@@ -1134,156 +1135,285 @@ def _conv_backward(desc, x, dy, wd, need_dx, need_dw, dy_cb=None, x_cb=None, dy_
     return dx, dw
 
 
-def _channel_reduce(dy, y, z, mean, rstd, relu, gamma=None, want_bound=False, train=True, y_cb=None, zmask_beta=None, rmask=None):
+# Where the BatchNorm backward of a group takes its ReLU mask from: ONE value per group and pass, which ``_channel_reduce`` and
+# ``_bn_bwd_apply`` map to their entry points -- the reduce and the apply kernel of a group must see the same mask.
+MASK_NONE = "none"   # no ReLU
+MASK_Y = "y"         # the fp32 activation
+MASK_Y_CB = "y_cb"   # the sign of the leading piece of the activation's companion (compact storage, the 2-byte chain)
+MASK_Z = "z"         # recomputed from z: y > 0 <=> fma(z, gamma rstd, beta - mean gamma rstd) > 0 (BN_ZMASK; no residual enters)
+MASK_BITS = "bits"   # the bit-plane the forward pass wrote (RELU_MASK; an fp32 residual)
+
+
+def _channel_reduce(dy, mask=MASK_NONE, src=None, z=None, mean=None, rstd=None, gamma=None, beta=None, want_bound=False, train=True):
     """(dgamma, dbeta) of a BN (z given) or just the per-channel sum of dy (z None); with ``want_bound`` also the device
-    scalar bounding |dz| of the tensor bn_bwd_apply will write from these sums (include/mcdseg.h).  ``zmask_beta``: the group
-    has a ReLU and no residual, so the mask is recomputed from z and ``y`` is not read."""
+    scalar bounding |dz| of the tensor bn_bwd_apply will write from these sums (include/mcdseg.h).  ``mask`` / ``src``: where the
+    ReLU mask comes from (MASK_*) and the tensor that holds it -- y, its companion, the bit-plane; MASK_Z reads z and ``beta``."""
     L = lib()
-    n, c = dy.shape[0], dy.shape[1]
-    hw = dy.shape[2] * dy.shape[3]
+    n, c, hw = dy.shape[0], dy.shape[1], dy.shape[2] * dy.shape[3]
     ws = _ws(L.mcdseg_bn_bwd_workspace_bytes(n, c, hw), dy.device)
     dgamma = torch.empty(c, dtype=torch.float32, device=dy.device) if z is not None else None
     dbeta = torch.empty(c, dtype=torch.float32, device=dy.device)
     bound = torch.empty(1, dtype=torch.float32, device=dy.device) if want_bound else None
-    if rmask is not None:  # a ReLU group with residual: the mask from its bit-plane (``RELU_MASK``), y is not read
+    tail = (int(train), n, c, hw, _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream())
+    if mask == MASK_BITS:
         with _timed("bn_bwd_reduce", (0, 4 * n * c * hw * 2)):
-            check(L.mcdseg_bn_bwd_reduce_mask(_p(dy), _p(rmask), _p(z), _p(mean), _p(rstd), _p(gamma) if want_bound else None, _p(dgamma),
-                                              _p(dbeta), _p(bound), int(train), n, c, hw, _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()),
-                  "bn_bwd_reduce_mask")
-        return dgamma, dbeta, bound
-    if zmask_beta is not None:
+            check(L.mcdseg_bn_bwd_reduce_mask(_p(dy), _p(src), _p(z), _p(mean), _p(rstd), _p(gamma) if want_bound else None, _p(dgamma),
+                                              _p(dbeta), _p(bound), *tail), "bn_bwd_reduce_mask")
+    elif mask == MASK_Z:
         with _timed("bn_bwd_reduce", (0, 4 * n * c * hw * 2)):
-            check(L.mcdseg_bn_bwd_reduce_zmask(_p(dy), _p(z), _p(mean), _p(rstd), _p(gamma), _p(zmask_beta), _p(dgamma), _p(dbeta), _p(bound),
-                                               int(train), n, c, hw, _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()),
-                  "bn_bwd_reduce_zmask")
-        return dgamma, dbeta, bound
-    with _timed("bn_bwd_reduce", (0, 4 * n * c * hw * (1 + (y is not None) + (z is not None)))):
-        check(L.mcdseg_bn_bwd_reduce(_p(dy), _p(y), _p(y_cb) if y is None else None, MATH_ID.get(CONV_MATH, 0), _p(z), _p(mean), _p(rstd),
-                                     _p(dgamma), _p(dbeta), _p(gamma) if want_bound else None, _p(bound), int(train), n, c, hw,
-                                     int(relu), _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()), "bn_bwd_reduce")
+            check(L.mcdseg_bn_bwd_reduce_zmask(_p(dy), _p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dgamma), _p(dbeta), _p(bound),
+                                               *tail), "bn_bwd_reduce_zmask")
+    else:
+        with _timed("bn_bwd_reduce", (0, 4 * n * c * hw * (1 + (mask == MASK_Y) + (z is not None)))):
+            check(L.mcdseg_bn_bwd_reduce(_p(dy), _p(src) if mask == MASK_Y else None, _p(src) if mask == MASK_Y_CB else None,
+                                         MATH_ID.get(CONV_MATH, 0), _p(z), _p(mean), _p(rstd), _p(dgamma), _p(dbeta),
+                                         _p(gamma) if want_bound else None, _p(bound), int(train), n, c, hw, int(mask != MASK_NONE),
+                                         *tail[4:]), "bn_bwd_reduce")
     return dgamma, dbeta, bound
+
+
+def _bn_bwd_apply(dy, mask, src, use_cb, z, mean, rstd, gamma, beta, dgamma, dbeta, dz, dres, dz_bound, train):
+    """the apply pass behind ``_channel_reduce``, with the same mask source: writes ``dz`` (unless None), ``dres`` (the residual's
+    gradient, when the ReLU makes it differ from dy) and -- ``use_cb`` -- the pre-split companion of dz, which it returns.  The plain
+    kernel has no form that recomputes the mask from z: for MASK_Z it reads ``src`` = y, which exists whenever it runs."""
+    L = lib()
+    n, c, hw = dy.shape[0], dy.shape[1], dy.shape[2] * dy.shape[3]
+    elems, relu = n * c * hw, mask != MASK_NONE
+    p_dres = _p(dres) if relu else None
+    rd = 4 * elems * (2 + int(relu)) + 4 * elems * ((dz is not None) + (p_dres is not None))
+    if not use_cb:
+        with _timed("bn_bwd_apply", (0, rd)):
+            check(L.mcdseg_bn_bwd_apply(_p(dy), _p(src), _p(z), _p(mean), _p(rstd), _p(gamma), _p(dgamma), _p(dbeta), _p(dz), p_dres, n, c,
+                                        hw, int(relu), int(train), _stream()), "bn_bwd_apply")
+        return None
+    dz_cb = _cb_alloc(n, c, hw, dy.device)
+    math, rd = MATH_ID[CONV_MATH], rd + 2 * PIECES[CONV_MATH] * elems
+    if mask == MASK_Z:
+        with _timed("bn_bwd_apply_cb", (0, rd - 4 * elems)):
+            check(L.mcdseg_bn_bwd_apply_cb_zmask(_p(dy), _p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dgamma), _p(dbeta), _p(dz),
+                                                 _p(dz_cb), _p(dz_bound), math, n, c, hw, int(train), _stream()), "bn_bwd_apply_cb_zmask")
+    elif mask == MASK_BITS:
+        with _timed("bn_bwd_apply_cb", (0, rd - 4 * elems)):
+            check(L.mcdseg_bn_bwd_apply_cb_mask(_p(dy), _p(src), _p(z), _p(mean), _p(rstd), _p(gamma), _p(dgamma), _p(dbeta), _p(dz), p_dres,
+                                                _p(dz_cb), _p(dz_bound), math, n, c, hw, int(train), _stream()), "bn_bwd_apply_cb_mask")
+    else:
+        with _timed("bn_bwd_apply_cb", (0, rd)):
+            check(L.mcdseg_bn_bwd_apply_cb(_p(dy), _p(src) if mask == MASK_Y else None, _p(src) if mask == MASK_Y_CB else None, _p(z),
+                                           _p(mean), _p(rstd), _p(gamma), _p(dgamma), _p(dbeta), _p(dz), p_dres, _p(dz_cb), _p(dz_bound),
+                                           math, n, c, hw, int(relu), int(train), _stream()), "bn_bwd_apply_cb")
+    return dz_cb
 
 
 DEBUG_TAPE = None  # a list: _ConvBNAct.backward appends its intermediate tensors (development only)
 
 
 # ------------------------------------------------------------------------------------------------ conv + BN + act
+def _cb_grid_ok(n, c):
+    """the companion kernels put N * C/8 on grid y"""
+    return n * (c // 8) <= 65535
+
+
+def _uncut(desc, wgrad_cb=None):
+    """the batch goes through in one launch (arguments: ``_batch_pieces``)"""
+    return len(_batch_pieces(desc, wgrad_cb)) == 1
+
+
+def _wgrad_reads_cb(desc):
+    """the weight gradient has a plan that reads both pre-split companions and nothing else"""
+    return bool(_wgrad_split_plan(desc, True)) and desc.Cin % 8 == 0 and desc.Cout % 8 == 0
+
+
+class _GroupPlan:
+    """Every host decision of one conv + BN + act group, as plain values: it hangs on ``ctx`` and must keep no tensor alive.
+    ``_plan_forward`` fills the first row of slots when the group is called, ``_plan_backward`` the second at the top of a backward pass."""
+    __slots__ = ("relu", "training", "has_bias", "has_res", "res_half", "storage", "want_cb", "bits", "y_bound", "stem_window", "x_fp32",
+                 "x_virtual", "res_fp32",
+                 "stem_tr", "use_cb", "mask", "want_bound", "wgrad_cb", "skip_dz", "y_fp32", "x_fp32_bwd")
+    half = property(lambda self: self.storage == "half")        # the 2-byte chain (HALF_STORAGE)
+    compact = property(lambda self: self.storage != "fp32")     # no fp32 y is written: the companion IS the activation (ACT_STORAGE)
+
+
+def _plan_forward(desc, split_w, relu, training, has_bias, x_cb, x_virtual, has_res=False, res_virtual=False, res_cb=False, res_half=False,
+                  compact=False, single_piece_only=False, thin_ok=False, no_cb=False, half=False, needs_grad=True):
+    """The forward decisions of a group, from its descriptor, the module flags (read now) and what the caller passed.  Tensors enter as
+    booleans -- ``x_cb`` / ``res_cb``: it came with a companion; ``*_virtual``: it exists as its companion only; ``res_half``: it is an
+    activation of the 2-byte chain; ``split_w``: the packed weights are those of the split kernels -- so no GPU is needed to ask."""
+    p = _GroupPlan()
+    c, math = desc.Cout, MATH_ID.get(CONV_MATH, 0)
+    p.relu, p.training, p.has_bias, p.has_res, p.res_half = relu, training, has_bias, has_res, res_half
+    uncut, grid_ok = _uncut(desc), _cb_grid_ok(desc.N, c)
+    # this consumer reads fp32: x is materialised first (a batch cut along N keeps its companions -- the split kernels take slices,
+    # mcdseg.h Ncb -- except on the thin layers' window kernels, Cin <= 16)
+    p.x_fp32 = bool(x_virtual and not (split_w and x_cb and (uncut or desc.Cin > 16)))
+    p.x_virtual = bool(x_virtual and not p.x_fp32)
+    # the stem: forward on the LDS-window kernel from the zero-padded companion of the network input
+    p.stem_window = bool(STEM_WINDOW and split_w and not x_cb and not has_bias and PRESPLIT and desc.Cin % 8 != 0 and not p.x_virtual and uncut
+                         and lib().mcdseg_conv_split_window_ok(ctypes.byref(desc), math, 1, 0))
+    # the 2-byte chain: this group keeps z, y, dz and the gradients it hands on as one 16-bit value per element (not the thin layers,
+    # Cin <= 16: their window weight gradient multiplies BOTH pieces of dz's companion whatever the arithmetic)
+    is_half = bool(half and training and split_w and x_cb and not has_bias and _cb_wanted(c) and desc.Cin > 16 and grid_ok and not no_cb
+                   and (not has_res or (res_half and res_cb)) and lib().mcdseg_conv_split_half_ok(ctypes.byref(desc), math, 0)
+                   and _wgrad_reads_cb(desc))
+    # the pre-split companion of y: the scaled arithmetic needs |y|'s bound BEFORE y is written -- train-mode statistics
+    # give one (Samuelson), eval-mode running statistics do not (the consumer then measures y)
+    p.want_cb = bool(_cb_wanted(c) and grid_ok and (training or not _scaled()) and not no_cb)
+    is_compact = bool(compact and p.want_cb and training)
+    if is_compact and single_piece_only and c <= 32 and not (thin_ok and c >= 16 and uncut):
+        is_compact = False  # the consumer would run its weight gradient on the f32 kernels and read fp32
+    p.storage = "half" if is_half else "compact" if is_compact else "fp32"
+    p.res_fp32 = bool(res_virtual and not p.want_cb)  # plain bn_apply reads fp32: the residual is materialised first
+    p.y_bound = bool(training and _scaled() and _use_split(c))  # with or without a companion: consumers that split y themselves use it too
+    # the ReLU bit-plane for this group's backward pass (``_bn_apply`` takes it back where the geometry or the alignment has none)
+    p.bits = bool(p.want_cb and RELU_MASK and relu and has_res and training and p.storage == "fp32" and not (res_virtual and res_cb)
+                  and needs_grad)
+    return p
+
+
+def _plan_backward(p, desc, split_d, need_x, need_w, need_bias, x_cb, dy_aligned=True):
+    """The backward decisions of a group, taken once at the top of a backward pass: what autograd asks for (``need_*``) and the
+    alignment of ``dy`` are only known there.  ``split_d``: the data-gradient weights are those of the split kernels; ``x_cb``: the
+    input came with a companion."""
+    n, c = desc.N, desc.Cout
+    if p.half:  # dz exists as the leading companion piece alone, and the convolution's gradients come from companions alone
+        if need_w and not _wgrad_reads_cb(desc):
+            raise RuntimeError("mcdseg: a group of the 2-byte chain needs a weight-gradient plan that reads companions (%d -> %d channels)"
+                               % (desc.Cin, desc.Cout))
+        p.stem_tr = p.y_fp32 = p.x_fp32_bwd = False
+        p.use_cb = p.want_bound = p.wgrad_cb = p.skip_dz = True
+        p.mask = MASK_NONE if not p.relu else MASK_Y_CB if p.has_res else MASK_Z
+        return p
+    # the stem: no input gradient and an input without a companion, but its weight gradient runs on split operands too
+    # (conv_wgrad_thin_tr.hip) -- from the zero-padded companion of the network input and the companion of dz
+    p.stem_tr = bool(need_w and not need_x and not x_cb and desc.Cin % 8 != 0 and PRESPLIT and not p.x_virtual and _uncut(desc, True)
+                     and c % 8 == 0 and _cb_grid_ok(n, c) and _wgrad_thin_tr(desc))
+    x_cb = x_cb or p.stem_tr
+    p.use_cb = p.stem_tr or bool((need_x or (need_w and x_cb)) and split_d and _cb_wanted(c) and _cb_grid_ok(n, c))
+    p.y_fp32 = p.compact and not p.use_cb  # the plain backward kernels read the fp32 activation for the ReLU mask: y is materialised
+    if not p.relu:
+        p.mask = MASK_NONE
+    elif BN_ZMASK and not p.has_res and (not p.compact or p.use_cb):
+        p.mask = MASK_Z
+    elif p.bits and p.use_cb and dy_aligned:  # (where the four-pixel backward kernel will run)
+        p.mask = MASK_BITS
+    else:
+        p.mask = MASK_Y_CB if (p.compact and p.use_cb) else MASK_Y
+    p.want_bound = bool(_scaled() and (split_d or p.stem_tr or _wgrad_split_plan(desc)))
+    # the fp32 dz is skipped when every consumer reads the split companion: dgrad (pre-split gather) and wgrad (pre-split plans); a conv
+    # bias gradient or any fallback path still needs it (cut batches keep their companions, see ``_plan_forward``; the stem's window
+    # weight gradient takes the whole batch's companions whatever the forward pass was cut into)
+    single = p.stem_tr or _uncut(desc) or desc.Cin > 16
+    p.wgrad_cb = p.stem_tr or bool(x_cb and p.use_cb and single and _wgrad_reads_cb(desc))
+    p.skip_dz = bool(p.use_cb and single and not (p.has_bias and need_bias) and (not need_w or p.wgrad_cb))
+    p.x_fp32_bwd = bool(p.x_virtual and need_w and not p.wgrad_cb)  # the weight gradient falls back to a kernel that reads fp32
+    return p
+
+
+def _bn_apply(plan, desc, z, z_bound, mean, rstd, gamma, beta, residual, res_cb, res_bound, y_bound):
+    """y = act(bn(z) + residual) in the group's storage form: (y or its stand-in, the companion, the ReLU bit-plane)"""
+    L = lib()
+    n, c, hw, dev = desc.N, desc.Cout, desc.Ho * desc.Wo, z.device
+    elems, has_res, relu = n * c * hw, plan.has_res, int(plan.relu)
+    if plan.half:
+        y_cb = torch.empty(elems, dtype=torch.int16, device=dev)   # ONE piece: the activation
+        with _timed("bn_apply_half", (0, elems * (4 + (2 if has_res else 0)))):
+            check(L.mcdseg_bn_apply_half(_p(z), _p(z_bound), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(res_cb) if has_res else None,
+                                         _p(res_bound) if has_res else None, _p(y_cb), _p(y_bound), n, c, hw, relu, _stream()), "bn_apply_half")
+        return _virtual((n, c, desc.Ho, desc.Wo), dev, torch.bfloat16), y_cb, None
+    y = _virtual(z.shape, dev) if plan.compact else torch.empty_like(z)
+    if not plan.want_cb:
+        with _timed("bn_apply", (0, elems * (8 + (4 if has_res else 0)))):
+            check(L.mcdseg_bn_apply(_p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual), _p(y), n, c, hw, relu, _stream()), "bn_apply")
+        return y, None, None
+    rmask = None
+    if plan.bits and (z.data_ptr() | y.data_ptr() | residual.data_ptr()) % 16 == 0:
+        nbytes = L.mcdseg_bn_relu_mask_bytes(n, c, hw)
+        if nbytes > 0:
+            rmask = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    plan.bits = rmask is not None
+    y_cb = _cb_alloc(n, c, hw, dev)
+    math, cb_bytes = MATH_ID[CONV_MATH], 2 * PIECES[CONV_MATH]
+    if rmask is not None:
+        with _timed("bn_apply_cb", (0, elems * (4 + 4 + cb_bytes + 4) + rmask.numel() * 8)):
+            check(L.mcdseg_bn_apply_cb_mask(_p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual), _p(y), _p(y_cb), _p(y_bound),
+                                            _p(rmask), math, n, c, hw, _stream()), "bn_apply_cb_mask")
+    else:
+        with _timed("bn_apply_cb", (0, elems * (4 + (0 if plan.compact else 4) + cb_bytes + (4 if has_res else 0)))):
+            check(L.mcdseg_bn_apply_cb(_p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual) if res_cb is None else None,
+                                       _p(res_cb), _p(res_bound) if res_cb is not None else None, None if plan.compact else _p(y),
+                                       _p(y_cb), _p(y_bound), math, n, c, hw, relu, _stream()), "bn_apply_cb")
+    return y, y_cb, rmask
+
+
+# the arguments of ``_ConvBNAct.apply``, and so the slots of what its backward returns and of ``ctx.needs_input_grad``
+_GroupGrads = collections.namedtuple("_GroupGrads", "x weight gamma beta residual conv_bias call", defaults=(None,) * 7)
+
+
 class _ConvBNAct(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, residual, conv_bias, running_mean, running_var, nbt, packed, geom, training,
-                momentum, eps, relu, x_cb, x_bound, res_bound, aux):
-        """aux: dict(x_virtual, res_virtual, res_cb, compact) -- compact activation storage (see ACT_STORAGE)"""
+    def forward(ctx, x, weight, gamma, beta, residual, conv_bias, call):
         L = lib()
         if _FWD_SYNC == "follow":
             _fwd_sync_wait(gamma)  # (ForwardFork: the leading pass is through with this layer)
-        stride, pad, dil = geom
-        desc = conv_desc(x.shape, weight.shape, stride, pad, dil)
+        desc = conv_desc(x.shape, weight.shape, *call.geom)
+        packed, training = call.packed, call.training
         wf, wd, mpf = packed.get(getattr(weight, "_mcd_param", weight), desc)
-        w_bound = packed.w_bound
-        x_virtual = aux["x_virtual"]
-        x_half = bool(aux.get("x_half"))  # (decided on the tensor autograd knows, before a consumer of fp32 materializes it below)
-        # (a batch cut along N keeps its companions -- the split kernels take slices, mcdseg.h Ncb -- except on the thin layers'
-        # window kernels, Cin <= 16)
-        uncut = len(_batch_pieces(desc)) == 1
-        if x_virtual and not (_is_split(wf) and x_cb is not None and (uncut or desc.Cin > 16)):
-            x, x_virtual = materialize(x, x_cb, x_bound), False  # this consumer reads fp32
-        if not x_virtual:
+        w_bound, split_w = packed.w_bound, _is_split(wf)
+        x_cb, x_bound, res_cb, res_bound = call.x_cb, call.x_bound, call.res_cb, call.res_bound
+        plan = _plan_forward(desc, split_w, call.relu, training, conv_bias is not None, x_cb is not None, call.x_virtual, residual is not None,
+                             call.res_virtual, res_cb is not None, call.res_half, call.compact, call.single_piece_only, call.thin_ok,
+                             call.no_cb, call.half, any(ctx.needs_input_grad))
+        if plan.x_fp32:
+            x = materialize(x, x_cb, x_bound)
+        if not plan.x_virtual:
             x = _req(x, "conv input")
-        if _is_split(wf) and _scaled():
+        if split_w and _scaled():
             x_bound = _bound_or_measure(x, x_bound)
         f_cb = x_cb
-        if (STEM_WINDOW and _is_split(wf) and x_cb is None and conv_bias is None and PRESPLIT and desc.Cin % 8 != 0 and not x_virtual
-                and len(_batch_pieces(desc)) == 1 and L.mcdseg_conv_split_window_ok(ctypes.byref(desc), MATH_ID[CONV_MATH], 1, 0)):
-            # the stem: forward on the LDS-window kernel from the zero-padded companion of the network input (cached on the
-            # tensor: the same batch goes through the stem several times per MCD step, forward and weight gradient)
+        if plan.stem_window:  # (cached on the tensor: the same batch goes through the stem several times per MCD step)
             f_cb, x_bound = split_companion_padded(x, x_bound)
-        c = desc.Cout
-        hw = desc.Ho * desc.Wo
-        # the 2-byte chain (HALF_STORAGE): this group keeps z, y, dz and the gradients it hands on as one 16-bit value per element
-        # (not the thin layers, Cin <= 16: their window weight gradient multiplies BOTH pieces of dz's companion whatever the arithmetic)
-        half = bool(aux.get("half") and training and _is_split(wf) and x_cb is not None and conv_bias is None and _cb_wanted(c) and desc.Cin > 16
-                    and desc.N * (c // 8) <= 65535 and not aux.get("no_cb")
-                    and (residual is None or (aux["res_virtual"] and aux["res_cb"] is not None and residual.dtype == torch.bfloat16))
-                    and L.mcdseg_conv_split_half_ok(ctypes.byref(desc), MATH_ID[CONV_MATH], 0) and _wgrad_split_plan(desc, True))
-        if half:
-            return _ConvBNAct._forward_half(ctx, L, desc, x, weight, gamma, beta, residual, running_mean, running_var, nbt, packed, wf, wd, mpf,
-                                            w_bound, momentum, eps, relu, x_cb, x_bound, res_bound, aux)
-        z, part, rows = _conv_fprop(desc, x, wf, _req(conv_bias, "conv bias"), training, mpf, f_cb, x_bound, w_bound)
+        c, z_bound = desc.Cout, None
+        if plan.half:
+            z, z_bound, part, rows = _conv_fprop_half(desc, x_cb, x_bound, wf, w_bound, mpf)
+        else:
+            z, part, rows = _conv_fprop(desc, x, wf, _req(conv_bias, "conv bias"), training, mpf, f_cb, x_bound, w_bound)
         mean = torch.empty(c, dtype=torch.float32, device=z.device)
         rstd = torch.empty(c, dtype=torch.float32, device=z.device)
-        # the pre-split companion of y: the scaled arithmetic needs |y|'s bound BEFORE y is written -- train-mode statistics
-        # give one (Samuelson), eval-mode running statistics do not (the consumer then measures y)
-        want_cb = _cb_wanted(c) and desc.N * (c // 8) <= 65535 and (training or not _scaled()) and not aux.get("no_cb")
-        compact = aux["compact"] and want_cb and training
-        if compact and aux.get("single_piece_only") and c <= 32 and not (aux.get("thin_ok") and c >= 16 and len(_batch_pieces(desc)) == 1):
-            compact = False  # the consumer would run its weight gradient on the f32 kernels and read fp32
-        res_cb = aux["res_cb"] if aux["res_virtual"] else None
-        if aux["res_virtual"] and not want_cb:
-            residual, res_cb = materialize(residual, aux["res_cb"], res_bound), None  # plain bn_apply reads fp32
-        elif not aux["res_virtual"]:
-            residual = _req(residual, "residual")
-        has_res = residual is not None
-        y_bound = None
-        if training and _scaled() and _use_split(c):  # with or without a companion: consumers that split y themselves use it too
-            y_bound = torch.empty(1, dtype=torch.float32, device=z.device)
-            if has_res:
-                res_bound = _bound_or_measure(residual, res_bound)
+        if not call.res_virtual:
+            residual, res_cb = _req(residual, "residual"), None
+        elif plan.res_fp32:
+            residual, res_cb = materialize(residual, res_cb, res_bound), None
+        y_bound = torch.empty(1, dtype=torch.float32, device=z.device) if plan.y_bound else None
+        if plan.y_bound and plan.has_res:
+            res_bound = _bound_or_measure(residual, res_bound)
         if training:
-            track = running_mean is not None
+            track = call.running_mean is not None
             ws = torch.empty(L.mcdseg_bn_stats_workspace_bytes(rows, c) // 8 + 1, dtype=torch.float64, device=z.device)
             with _timed("bn_stats_finalize", (0, 12 * rows * mpf)):  # (one launch also when it stands for BN_RUNNING_REPEAT forward passes)
-                check(L.mcdseg_bn_stats_finalize(_p(part), rows, c, mpf, _p(mean), _p(rstd), _p(running_mean) if track else None,
-                                                 _p(running_var) if track else None, _p(nbt) if track else None,
-                                                 float(momentum), float(eps), _p(gamma) if y_bound is not None else None,
+                check(L.mcdseg_bn_stats_finalize(_p(part), rows, c, mpf, _p(mean), _p(rstd), _p(call.running_mean) if track else None,
+                                                 _p(call.running_var) if track else None, _p(call.nbt) if track else None,
+                                                 float(call.momentum), float(call.eps), _p(gamma) if y_bound is not None else None,
                                                  _p(beta) if y_bound is not None else None,
-                                                 _p(res_bound) if (y_bound is not None and has_res) else None, _p(y_bound),
+                                                 _p(res_bound) if (y_bound is not None and plan.has_res) else None, _p(y_bound),
                                                  int(BN_RUNNING_REPEAT if track else 1), _p(ws), ctypes.c_size_t(ws.numel() * 8), _stream()),
                       "bn_stats_finalize")
             if _FWD_SYNC == "lead":
                 _fwd_sync_record(gamma)
         else:
-            check(L.mcdseg_bn_eval_stats(_p(running_mean), _p(running_var), c, float(eps), _p(mean), _p(rstd), _stream()),
+            check(L.mcdseg_bn_eval_stats(_p(call.running_mean), _p(call.running_var), c, float(call.eps), _p(mean), _p(rstd), _stream()),
                   "bn_eval_stats")
-        y = _virtual(z.shape, z.device) if compact else torch.empty_like(z)
-        y_cb = None
-        elems = desc.N * c * hw
-        rmask = None
-        if (want_cb and RELU_MASK and relu and has_res and training and not compact and res_cb is None and any(ctx.needs_input_grad)
-                and (z.data_ptr() | y.data_ptr() | residual.data_ptr()) % 16 == 0):
-            nbytes = L.mcdseg_bn_relu_mask_bytes(desc.N, c, hw)
-            if nbytes > 0:  # the ReLU bit-plane for this group's backward pass (see RELU_MASK)
-                rmask = torch.empty(nbytes // 8, dtype=torch.int64, device=z.device)
-        if rmask is not None:
-            y_cb = _cb_alloc(desc.N, c, hw, z.device)
-            with _timed("bn_apply_cb", (0, elems * (4 + 4 + 2 * PIECES[CONV_MATH] + 4) + rmask.numel() * 8)):
-                check(L.mcdseg_bn_apply_cb_mask(_p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual), _p(y), _p(y_cb), _p(y_bound),
-                                                _p(rmask), MATH_ID[CONV_MATH], desc.N, c, hw, _stream()), "bn_apply_cb_mask")
-        elif want_cb:
-            y_cb = _cb_alloc(desc.N, c, hw, z.device)
-            with _timed("bn_apply_cb", (0, elems * (4 + (0 if compact else 4) + 2 * PIECES[CONV_MATH] + (4 if has_res else 0)))):
-                check(L.mcdseg_bn_apply_cb(_p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual) if res_cb is None else None,
-                                           _p(res_cb), _p(res_bound) if res_cb is not None else None, None if compact else _p(y),
-                                           _p(y_cb), _p(y_bound), MATH_ID[CONV_MATH], desc.N, c, hw, int(relu), _stream()), "bn_apply_cb")
-        else:
-            with _timed("bn_apply", (0, elems * (8 + (4 if has_res else 0)))):
-                check(L.mcdseg_bn_apply(_p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(residual), _p(y), desc.N, c, hw, int(relu),
-                                        _stream()), "bn_apply")
-        ctx.desc, ctx.wd, ctx.relu, ctx.training, ctx.has_res = desc, wd, relu, training, has_res
-        ctx.w_bound = w_bound
+        y, y_cb, rmask = _bn_apply(plan, desc, z, z_bound, mean, rstd, gamma, beta, residual, res_cb, res_bound, y_bound)
+        ctx.plan, ctx.desc, ctx.wd, ctx.w_bound = plan, desc, wd, w_bound
         ctx.packed, ctx.pack_key = packed, packed.key  # the data-gradient image is shared and re-packed in place: see backward
         ctx.defer_ok = hasattr(weight, "_mcd_param")  # the weight came through a _LateGrad alias (late_weight_grads)
         ctx.w_param = getattr(weight, "_mcd_param", None)
         if ctx.w_param is None and getattr(weight, "_mcd_grad_sink", None) is not None:
             ctx.w_param = weight  # (no alias -- a second use of the module in one graph: its gradient is reported to the sink as "not early")
-        ctx.in_box, ctx.res_box = aux.get("in_box"), aux.get("res_box")
-        ctx.has_bias = conv_bias is not None
+        ctx.in_box, ctx.res_box = call.in_box, call.res_box
         ctx.x_cb, ctx.x_bound = x_cb, x_bound  # wgrad reads the input's split companion too (an input of this node: safe to hold)
-        ctx.x_virtual, ctx.compact = x_virtual, compact
-        ctx.rmask = rmask
-        ctx.half = False
-        ctx.x_half = x_half        # the gradients owed to activations of the 2-byte chain: bf16 units
-        ctx.res_half = bool(aux.get("res_half"))
-        ctx.save_for_backward(x, z, y, mean, rstd, gamma, y_cb if compact else None, y_bound if compact else None, beta)
+        ctx.rmask, ctx.z_bound = rmask, z_bound
+        ctx.x_half = call.x_half  # the gradient owed to an activation of the 2-byte chain: bf16 units
+        keep = plan.compact  # (the companion IS the activation; an fp32 group's backward reads y)
+        ctx.save_for_backward(x, z, y, mean, rstd, gamma, y_cb if keep else None, y_bound if keep else None, beta)
         ctx.set_materialize_grads(False)  # no zero-filled "gradient" for the non-differentiable companions
         for t in (y_cb, y_bound):
             if t is not None:
@@ -1291,194 +1421,66 @@ class _ConvBNAct(torch.autograd.Function):
         return y, y_cb, y_bound
 
     @staticmethod
-    def _forward_half(ctx, L, desc, x, weight, gamma, beta, residual, running_mean, running_var, nbt, packed, wf, wd, mpf, w_bound, momentum,
-                      eps, relu, x_cb, x_bound, res_bound, aux):
-        """the group in the 2-byte chain (HALF_STORAGE; include/mcdseg.h "2-byte activation storage"): train mode, pre-split input"""
-        c, hw = desc.Cout, desc.Ho * desc.Wo
-        dev = x_cb.device
-        has_res = residual is not None
-        z16, z_bound, part, rows = _conv_fprop_half(desc, x_cb, x_bound, wf, w_bound, mpf)
-        mean = torch.empty(c, dtype=torch.float32, device=dev)
-        rstd = torch.empty(c, dtype=torch.float32, device=dev)
-        y_bound = torch.empty(1, dtype=torch.float32, device=dev)
-        track = running_mean is not None
-        ws = torch.empty(L.mcdseg_bn_stats_workspace_bytes(rows, c) // 8 + 1, dtype=torch.float64, device=dev)
-        with _timed("bn_stats_finalize", (0, 12 * rows * mpf)):
-            check(L.mcdseg_bn_stats_finalize(_p(part), rows, c, mpf, _p(mean), _p(rstd), _p(running_mean) if track else None,
-                                             _p(running_var) if track else None, _p(nbt) if track else None, float(momentum), float(eps),
-                                             _p(gamma), _p(beta), _p(res_bound) if has_res else None, _p(y_bound),
-                                             int(BN_RUNNING_REPEAT if track else 1), _p(ws), ctypes.c_size_t(ws.numel() * 8), _stream()),
-                  "bn_stats_finalize")
-        if _FWD_SYNC == "lead":
-            _fwd_sync_record(gamma)
-        y_cb = torch.empty(desc.N * c * hw, dtype=torch.int16, device=dev)   # ONE piece: the activation
-        with _timed("bn_apply_half", (0, desc.N * c * hw * (4 + (2 if has_res else 0)))):
-            check(L.mcdseg_bn_apply_half(_p(z16), _p(z_bound), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(aux["res_cb"]) if has_res else None,
-                                         _p(res_bound) if has_res else None, _p(y_cb), _p(y_bound), desc.N, c, hw, int(relu), _stream()),
-                  "bn_apply_half")
-        y = _virtual((desc.N, c, desc.Ho, desc.Wo), dev, torch.bfloat16)
-        ctx.desc, ctx.wd, ctx.relu, ctx.training, ctx.has_res = desc, wd, relu, True, has_res
-        ctx.w_bound = w_bound
-        ctx.packed, ctx.pack_key = packed, packed.key
-        ctx.defer_ok = hasattr(weight, "_mcd_param")
-        ctx.w_param = getattr(weight, "_mcd_param", None)
-        if ctx.w_param is None and getattr(weight, "_mcd_grad_sink", None) is not None:
-            ctx.w_param = weight
-        ctx.in_box, ctx.res_box = aux.get("in_box"), aux.get("res_box")
-        ctx.has_bias = False
-        ctx.x_cb, ctx.x_bound = x_cb, x_bound
-        ctx.x_virtual, ctx.compact = aux["x_virtual"], True
-        ctx.rmask = None
-        ctx.half = True
-        ctx.x_half = bool(aux.get("x_half"))
-        ctx.res_half = has_res
-        ctx.z_bound = z_bound
-        ctx.save_for_backward(x, z16, y, mean, rstd, gamma, y_cb, y_bound, beta)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(y_cb, y_bound)
-        return y, y_cb, y_bound
-
-    @staticmethod
-    def _backward_half(ctx, dy):
-        """backward of a group of the 2-byte chain: ``dy`` bf16 units -> dz as the leading companion piece, the residual's gradient as bf16
-        units, then the convolution's gradients from companions alone"""
-        L = lib()
-        x, z16, y, mean, rstd, gamma, y_cb, y_bound, beta = ctx.saved_tensors
-        desc = ctx.desc
-        if ctx.packed.key != ctx.pack_key:
-            raise RuntimeError("mcdseg: a convolution weight was modified between a forward pass and its backward pass "
-                               "(an optimizer stepped the generator while its graph was still alive)")
-        dy = _req(dy, "grad_output", torch.bfloat16)
-        n, c, hw = desc.N, desc.Cout, desc.Ho * desc.Wo
-        dev = dy.device
-        mask = 0 if not ctx.relu else (4 if ctx.has_res else 2)
-        ws = _ws(L.mcdseg_bn_bwd_half_workspace_bytes(n, c, hw), dev)
-        dgamma = torch.empty(c, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(c, dtype=torch.float32, device=dev)
-        dz_bound = torch.empty(1, dtype=torch.float32, device=dev)
-        elems = n * c * hw
-        with _timed("bn_bwd_reduce_half", (0, elems * (4 + (2 if mask == 4 else 0)))):
-            check(L.mcdseg_bn_bwd_reduce_half(_p(dy), _p(y_cb) if mask == 4 else None, _p(z16), _p(ctx.z_bound), _p(mean), _p(rstd), _p(gamma),
-                                              _p(beta), _p(dgamma), _p(dbeta), _p(dz_bound), mask, 1, n, c, hw, _p(ws),
-                                              ctypes.c_size_t(ws.numel() * 4), _stream()), "bn_bwd_reduce_half")
-        dz_cb = torch.empty(elems, dtype=torch.int16, device=dev)
-        dres = None
-        if ctx.has_res and ctx.needs_input_grad[4]:
-            dres = torch.empty_like(dy) if ctx.relu else dy
-        with _timed("bn_bwd_apply_half", (0, elems * (6 + (2 if mask == 4 else 0) + (2 if (dres is not None and ctx.relu) else 0)))):
-            check(L.mcdseg_bn_bwd_apply_half(_p(dy), _p(y_cb) if mask == 4 else None, _p(z16), _p(ctx.z_bound), _p(mean), _p(rstd), _p(gamma),
-                                             _p(beta), _p(dgamma), _p(dbeta), _p(dz_cb), _p(dz_bound),
-                                             _p(dres) if (dres is not None and ctx.relu) else None, mask, 1, n, c, hw, _stream()),
-                  "bn_bwd_apply_half")
-        if ctx.res_box is not None and dres is not None:
-            other, last = ctx.res_box.arrive()
-            if last:
-                dres = dres if other is None else dres + other
-            else:
-                ctx.res_box.leave(dres if other is None else dres + other)
-                dres = None
-        addend, dx_last = (None, True)
-        if ctx.in_box is not None and ctx.needs_input_grad[0]:
-            addend, dx_last = ctx.in_box.arrive()
-        if ctx.needs_input_grad[1] and not (_wgrad_split_plan(desc, True) and desc.Cin % 8 == 0 and desc.Cout % 8 == 0):
-            raise RuntimeError("mcdseg: a group of the 2-byte chain needs a weight-gradient plan that reads companions (%d -> %d channels)"
-                               % (desc.Cin, desc.Cout))
-        dx, dw = _conv_backward(desc, x, None, ctx.wd, ctx.needs_input_grad[0], ctx.needs_input_grad[1], dz_cb, ctx.x_cb, dz_bound,
-                                ctx.x_bound, ctx.w_bound, defer=ctx.defer_ok, param=ctx.w_param, dx_addend=addend, dx16=ctx.x_half)
-        if not dx_last:
-            ctx.in_box.leave(dx)
-            dx = None
-        return (dx, dw, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, dres, None,
-                None, None, None, None, None, None, None, None, None, None, None, None, None)
-
-    @staticmethod
     def backward(ctx, dy, _dcb=None, _dbound=None):
-        L = lib()
         if dy is None:
-            return (None,) * 19
-        if ctx.half:
-            return _ConvBNAct._backward_half(ctx, dy)
+            return tuple(_GroupGrads())
+        L = lib()
+        plan, desc = ctx.plan, ctx.desc
         x, z, y, mean, rstd, gamma, y_cb, y_bound, beta = ctx.saved_tensors
-        desc = ctx.desc
         if ctx.packed.key != ctx.pack_key:
             # the weight was updated in place (and its packed image re-packed) between this forward and its backward: the data gradient
             # would use the NEW weights -- what torch reports for a saved tensor as "modified by an inplace operation"
             raise RuntimeError("mcdseg: a convolution weight was modified between a forward pass and its backward pass "
                                "(an optimizer stepped the generator while its graph was still alive)")
-        dy = _req(dy, "grad_output")
+        need = _GroupGrads(*ctx.needs_input_grad)
+        dy = _req(dy, "grad_output", torch.bfloat16 if plan.half else torch.float32)
+        _plan_backward(plan, desc, _is_split(ctx.wd), need.x, need.weight, need.conv_bias, ctx.x_cb is not None, dy.data_ptr() % 16 == 0)
         n, c, hw = desc.N, desc.Cout, desc.Ho * desc.Wo
-        split_d = _is_split(ctx.wd)
         x_cb, x_bound = ctx.x_cb, ctx.x_bound
-        # the stem: no input gradient and an input without a companion, but its weight gradient runs on split operands too
-        # (conv_wgrad_thin_tr.hip) -- from the zero-padded companion of the network input and the companion of dz
-        stem_tr = (ctx.needs_input_grad[1] and not ctx.needs_input_grad[0] and x_cb is None and desc.Cin % 8 != 0 and PRESPLIT
-                   and not ctx.x_virtual and len(_batch_pieces(desc, wgrad_cb=True)) == 1 and c % 8 == 0 and n * (c // 8) <= 65535
-                   and _wgrad_thin_tr(desc))
-        if stem_tr:
+        if plan.stem_tr:
             x_cb, x_bound = split_companion_padded(x)
-        want_cb = ctx.needs_input_grad[0] or (ctx.needs_input_grad[1] and x_cb is not None)
-        use_cb = stem_tr or (want_cb and split_d and _cb_wanted(c) and n * (c // 8) <= 65535)
-        # a ReLU group without residual: y > 0 <=> fma(z, gamma rstd, beta - mean gamma rstd) > 0 -- neither pass below reads y
-        zmask = BN_ZMASK and ctx.relu and not ctx.has_res and (y_cb is None or use_cb)
-        if ctx.compact and not use_cb:  # the plain backward kernels read the fp32 activation for the ReLU mask
-            y, y_cb = materialize(y, y_cb, y_bound), None
-        y_mask = (y if y_cb is None else None) if ctx.relu else None
-        # a ReLU group with residual: the mask from the bit-plane the forward pass wrote, where the four-pixel backward kernel will run
-        rmask = ctx.rmask if (ctx.relu and use_cb and not zmask and dy.data_ptr() % 16 == 0) else None
-        dgamma, dbeta, dz_bound = _channel_reduce(dy, y_mask, z, mean, rstd, ctx.relu, gamma,
-                                                  want_bound=_scaled() and (split_d or stem_tr or _wgrad_split_plan(desc)), train=ctx.training,
-                                                  y_cb=y_cb if ctx.relu else None, zmask_beta=beta if zmask else None, rmask=rmask)
-        dz = None
-        dres = None
-        if ctx.has_res and ctx.needs_input_grad[4]:
-            dres = torch.empty_like(z) if ctx.relu else dy
-        dz_cb = None
-        # the fp32 dz is skipped when every consumer reads the split companion: dgrad (pre-split gather) and wgrad
-        # (pre-split plans); a conv bias gradient or any fallback path still needs it
-        # (cut batches keep their companions, see forward; the stem's window weight gradient takes the whole batch's companions whatever
-        # the forward pass was cut into)
-        single = single_piece = stem_tr or len(_batch_pieces(desc)) == 1 or desc.Cin > 16
-        wgrad_cb = stem_tr or (x_cb is not None and use_cb and single_piece and _wgrad_split_plan(desc, True) and desc.Cin % 8 == 0
-                               and desc.Cout % 8 == 0)
-        skip_dz = (use_cb and single and not (ctx.has_bias and ctx.needs_input_grad[5])
-                   and (not ctx.needs_input_grad[1] or wgrad_cb))
-        if not skip_dz:
-            dz = torch.empty_like(z)
-        rd = 4 * n * c * hw * (2 + int(ctx.relu)) + 4 * n * c * hw * ((dz is not None) + (dres is not None and ctx.relu))
-        if use_cb and zmask:
-            dz_cb = _cb_alloc(n, c, hw, dy.device)
-            with _timed("bn_bwd_apply_cb", (0, rd - 4 * n * c * hw + 2 * PIECES[CONV_MATH] * n * c * hw)):
-                check(L.mcdseg_bn_bwd_apply_cb_zmask(_p(dy), _p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dgamma), _p(dbeta), _p(dz),
-                                                     _p(dz_cb), _p(dz_bound), MATH_ID[CONV_MATH], n, c, hw, int(ctx.training), _stream()),
-                      "bn_bwd_apply_cb_zmask")
-        elif use_cb and rmask is not None:
-            dz_cb = _cb_alloc(n, c, hw, dy.device)
-            with _timed("bn_bwd_apply_cb", (0, rd - 4 * n * c * hw + 2 * PIECES[CONV_MATH] * n * c * hw)):
-                check(L.mcdseg_bn_bwd_apply_cb_mask(_p(dy), _p(rmask), _p(z), _p(mean), _p(rstd), _p(gamma), _p(dgamma), _p(dbeta), _p(dz),
-                                                    _p(dres) if dres is not None else None, _p(dz_cb), _p(dz_bound), MATH_ID[CONV_MATH], n, c,
-                                                    hw, int(ctx.training), _stream()), "bn_bwd_apply_cb_mask")
-        elif use_cb:
-            dz_cb = _cb_alloc(n, c, hw, dy.device)
-            with _timed("bn_bwd_apply_cb", (0, rd + 2 * PIECES[CONV_MATH] * n * c * hw)):
-                check(L.mcdseg_bn_bwd_apply_cb(_p(dy), _p(y_mask), _p(y_cb) if (ctx.relu and y_mask is None) else None, _p(z), _p(mean),
-                                               _p(rstd), _p(gamma), _p(dgamma), _p(dbeta), _p(dz),
-                                               _p(dres) if (dres is not None and ctx.relu) else None, _p(dz_cb), _p(dz_bound),
-                                               MATH_ID[CONV_MATH], n, c, hw, int(ctx.relu), int(ctx.training), _stream()),
-                      "bn_bwd_apply_cb")
+        dz = dres = None
+        if plan.half:
+            # ``dy`` bf16 units -> dz as the leading companion piece, the residual's gradient as bf16 units
+            mask = {MASK_NONE: 0, MASK_Z: 2, MASK_Y_CB: 4}[plan.mask]
+            src = _p(y_cb) if plan.mask == MASK_Y_CB else None
+            elems = n * c * hw
+            ws = _ws(L.mcdseg_bn_bwd_half_workspace_bytes(n, c, hw), dy.device)
+            dgamma = torch.empty(c, dtype=torch.float32, device=dy.device)
+            dbeta = torch.empty(c, dtype=torch.float32, device=dy.device)
+            dz_bound = torch.empty(1, dtype=torch.float32, device=dy.device)
+            with _timed("bn_bwd_reduce_half", (0, elems * (4 + (2 if mask == 4 else 0)))):
+                check(L.mcdseg_bn_bwd_reduce_half(_p(dy), src, _p(z), _p(ctx.z_bound), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dgamma),
+                                                  _p(dbeta), _p(dz_bound), mask, 1, n, c, hw, _p(ws), ctypes.c_size_t(ws.numel() * 4),
+                                                  _stream()), "bn_bwd_reduce_half")
+            dz_cb = torch.empty(elems, dtype=torch.int16, device=dy.device)
+            if plan.has_res and need.residual:
+                dres = torch.empty_like(dy) if plan.relu else dy
+            p_dres = _p(dres) if plan.relu else None
+            with _timed("bn_bwd_apply_half", (0, elems * (6 + (2 if mask == 4 else 0) + (2 if p_dres is not None else 0)))):
+                check(L.mcdseg_bn_bwd_apply_half(_p(dy), src, _p(z), _p(ctx.z_bound), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(dgamma),
+                                                 _p(dbeta), _p(dz_cb), _p(dz_bound), p_dres, mask, 1, n, c, hw, _stream()),
+                      "bn_bwd_apply_half")
         else:
-            with _timed("bn_bwd_apply", (0, rd)):
-                check(L.mcdseg_bn_bwd_apply(_p(dy), _p(y_mask), _p(z), _p(mean), _p(rstd), _p(gamma), _p(dgamma), _p(dbeta), _p(dz),
-                                            _p(dres) if (dres is not None and ctx.relu) else None, n, c, hw, int(ctx.relu),
-                                            int(ctx.training), _stream()), "bn_bwd_apply")
-        if ctx.x_virtual and ctx.needs_input_grad[1] and not (wgrad_cb and dz_cb is not None and single):
-            x = materialize(x, ctx.x_cb, ctx.x_bound)  # the weight gradient falls back to a kernel that reads fp32
-        if DEBUG_TAPE is not None:  # kernel development (tools/op_contention.py): what the BN backward handed to the conv backward
-            DEBUG_TAPE.append(dict(dy=dy, dz=dz, dz_cb=dz_cb, dz_bound=dz_bound, dgamma=dgamma, dbeta=dbeta, dres=dres, shape=(n, c, hw), z=z,
-                                   y=y_mask, mean=mean, rstd=rstd, gamma=gamma, beta=beta, zmask=zmask))
+            if plan.y_fp32:
+                y, y_cb = materialize(y, y_cb, y_bound), None
+            y_mask = (y if y_cb is None else None) if plan.relu else None
+            src = {MASK_NONE: None, MASK_Y: y_mask, MASK_Y_CB: y_cb, MASK_BITS: ctx.rmask, MASK_Z: None if plan.use_cb else y_mask}[plan.mask]
+            dgamma, dbeta, dz_bound = _channel_reduce(dy, plan.mask, src, z, mean, rstd, gamma, beta, plan.want_bound, plan.training)
+            if plan.has_res and need.residual:
+                dres = torch.empty_like(z) if plan.relu else dy
+            if not plan.skip_dz:
+                dz = torch.empty_like(z)
+            dz_cb = _bn_bwd_apply(dy, plan.mask, src, plan.use_cb, z, mean, rstd, gamma, beta, dgamma, dbeta, dz, dres, dz_bound, plan.training)
+            if plan.x_fp32_bwd:
+                x = materialize(x, ctx.x_cb, ctx.x_bound)
+            if DEBUG_TAPE is not None:  # kernel development (tools/op_contention.py): what the BN backward handed to the conv backward
+                DEBUG_TAPE.append(dict(dy=dy, dz=dz, dz_cb=dz_cb, dz_bound=dz_bound, dgamma=dgamma, dbeta=dbeta, dres=dres, shape=(n, c, hw),
+                                       z=z, y=y_mask, mean=mean, rstd=rstd, gamma=gamma, beta=beta, zmask=plan.mask == MASK_Z))
+            if dres is not None and plan.res_half:
+                dres = pack_bf16_units(dres)  # (the residual is an activation of the 2-byte chain: its gradient is owed as bf16 units)
         # the gradients this group shares with another producer (GradBox): the shortcut's goes into its box -- or comes back summed when
         # this group happens to be the last -- and the data gradient takes the box's tensor into its epilogue
-        if dres is not None and ctx.res_half:
-            dres = pack_bf16_units(dres)  # (the residual is an activation of the 2-byte chain: its gradient is owed as bf16 units)
         if ctx.res_box is not None and dres is not None:
             other, last = ctx.res_box.arrive()
             if last:
@@ -1486,21 +1488,17 @@ class _ConvBNAct(torch.autograd.Function):
             else:
                 ctx.res_box.leave(dres if other is None else dres + other)
                 dres = None
-        addend, dx_last = (None, True)
-        if ctx.in_box is not None and ctx.needs_input_grad[0]:
-            addend, dx_last = ctx.in_box.arrive()
-        dx, dw = _conv_backward(desc, x, dz, ctx.wd, ctx.needs_input_grad[0], ctx.needs_input_grad[1], dz_cb, x_cb, dz_bound,
-                                x_bound, ctx.w_bound, defer=ctx.defer_ok, param=ctx.w_param, dx_addend=addend, dx16=ctx.x_half)
+        addend, dx_last = ctx.in_box.arrive() if (ctx.in_box is not None and need.x) else (None, True)
+        dx, dw = _conv_backward(desc, x, dz, ctx.wd, need.x, need.weight, dz_cb, x_cb, dz_bound, x_bound, ctx.w_bound, defer=ctx.defer_ok,
+                                param=ctx.w_param, dx_addend=addend, dx16=ctx.x_half)
         if not dx_last:
             ctx.in_box.leave(dx)
             dx = None
-        dbias = None
-        if ctx.has_bias and ctx.needs_input_grad[5]:
-            # a bias in front of train-mode BN has zero gradient up to rounding (BN removes the channel mean);
-            # it is still formed, as autograd does in the reference (CBR, models/dilated_fcn.py:632-644)
-            _, dbias, _ = _channel_reduce(dz, None, None, None, None, False)
-        return (dx, dw, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None, dres, dbias,
-                None, None, None, None, None, None, None, None, None, None, None, None, None)
+        # a bias in front of train-mode BN has zero gradient up to rounding (BN removes the channel mean);
+        # it is still formed, as autograd does in the reference (CBR, models/dilated_fcn.py:632-644)
+        dbias = _channel_reduce(dz)[1] if (plan.has_bias and need.conv_bias) else None
+        return tuple(_GroupGrads(x=dx, weight=dw, gamma=dgamma if need.gamma else None, beta=dbeta if need.beta else None, residual=dres,
+                                 conv_bias=dbias))
 
 
 def _conv_bn_act_inference(x, conv, bn, relu, residual):
@@ -1553,25 +1551,23 @@ def conv_bn_act(x, conv, bn, relu=True, residual=None, internal=False, in_box=No
     res_cb, res_bound = _cb_of(residual) if residual is not None else (None, None)
     skip_y = internal and INTERNAL_SKIP_Y and BN_ZMASK and relu and residual is None and _scaled()
     grads = torch.is_grad_enabled()
-    aux = dict(x_virtual=is_virtual(x), res_virtual=is_virtual(residual), res_cb=res_cb, compact=_compact_now() or skip_y,
-               single_piece_only=skip_y and not _compact_now(), thin_ok=thin_ok,
-               no_cb=bool(shortcut_only and SHORTCUT_NO_CB and not relu and residual is None and not _compact_now()),
-               half=_half_now(), x_half=is_half(x), res_half=is_half(residual),
-               in_box=in_box.attach() if (in_box is not None and grads and x.requires_grad) else None,
-               res_box=res_box.attach() if (res_box is not None and grads and residual is not None and residual.requires_grad) else None)
-    y, y_cb, y_bound = _ConvBNAct.apply(x, _take_late(conv), bn.weight, bn.bias, residual, conv.bias, bn.running_mean if track else None,
-                                        bn.running_var if track else None, bn.num_batches_tracked if track else None, conv._packed,
-                                        geom, training, momentum, bn.eps, relu, x_cb, x_bound, res_bound, aux)
+    # what the Function needs beside the six tensors autograd must see (read in ``forward`` only: not kept on ``ctx``)
+    call = types.SimpleNamespace(running_mean=bn.running_mean if track else None, running_var=bn.running_var if track else None,
+                      nbt=bn.num_batches_tracked if track else None, packed=conv._packed, geom=geom, training=training, momentum=momentum,
+                      eps=bn.eps, relu=relu, x_cb=x_cb, x_bound=x_bound, res_cb=res_cb, res_bound=res_bound, x_virtual=is_virtual(x),
+                      res_virtual=is_virtual(residual), compact=_compact_now() or skip_y, single_piece_only=skip_y and not _compact_now(),
+                      thin_ok=thin_ok, no_cb=bool(shortcut_only and SHORTCUT_NO_CB and not relu and residual is None and not _compact_now()),
+                      half=_half_now(), x_half=is_half(x), res_half=is_half(residual),  # (x_half: on the tensor autograd knows)
+                      in_box=in_box.attach() if (in_box is not None and grads and x.requires_grad) else None,
+                      res_box=res_box.attach() if (res_box is not None and grads and residual is not None and residual.requires_grad) else None)
+    y, y_cb, y_bound = _ConvBNAct.apply(x, _take_late(conv), bn.weight, bn.bias, residual, conv.bias, call)
     if y_cb is not None or y_bound is not None:
-        _attach_cb(y, y_cb, y_bound)  # the pre-split companion (and the bound) travel with the tensor object to the next convolution
+        # the pre-split companion (and the bound) travel with the tensor object to the next convolution; they are only valid for the values
+        # y holds NOW: remember the autograd version counter and the storage
+        y._mcd_cb = (y_cb, y_bound, y._version, y.data_ptr())
     if y.stride(0) == 0 and y.numel() > 1:
         y._mcd_virtual = True  # compact storage: the companion IS the activation
     return y
-
-
-def _attach_cb(y, y_cb, y_bound=None):
-    # the companion (and the bound) is only valid for the values y holds NOW: remember the autograd version counter and the storage
-    y._mcd_cb = (y_cb, y_bound, y._version, y.data_ptr())
 
 
 def _cb_of(x):
@@ -1615,7 +1611,7 @@ class _Conv2dBias(torch.autograd.Function):
                                 ctx.w_bound)
         db = None
         if ctx.has_bias and ctx.needs_input_grad[2]:
-            _, db, _ = _channel_reduce(dy, None, None, None, None, False)
+            _, db, _ = _channel_reduce(dy)
         return dx, dw, db, None, None, None, None
 
 

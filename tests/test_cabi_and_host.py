@@ -541,3 +541,80 @@ def test_comm_entry_points_validate_their_arguments():
     assert L.mcdseg_comm_init(ctypes.byref(comm), 0, ident, 0) == -22
     assert L.mcdseg_comm_unique_id(None) == -22
     assert L.mcdseg_comm_destroy(None) == 0
+
+
+def _walk_group_plans(monkeypatch, net, n, h, w):
+    """(descriptor, plan, the call's flags) of every conv + BN group of a DRN trunk, train mode: the trunk is walked on meta tensors with a
+    shape-only ``conv_bn_act`` that hands the host facts of each output (companion, stand-in, 2-byte chain) to its consumers as the real one does"""
+    import ctypes
+    from mcdseg import ops
+    from models import drn
+    from models.dilated_fcn import Trunk
+    L, out = ops.lib(), []
+
+    def facts(t):
+        return getattr(t, "_facts", dict(cb=False, virtual=False, half=False))
+
+    def group(x, conv, bn, relu=True, residual=None, internal=False, in_box=None, res_box=None, thin_ok=False, shortcut_only=False):
+        desc = ops.conv_desc(x.shape, conv.weight.shape, conv.stride[0], conv.padding[0], conv.dilation[0])
+        split_w = ops._use_split(desc.Cin) or (ops.CONV_MATH in ops.MATH_ID and bool(L.mcdseg_conv_split_direct_ok(ctypes.byref(desc))))
+        fx, fr = facts(x), facts(residual)
+        skip_y = bool(internal and ops.INTERNAL_SKIP_Y and ops.BN_ZMASK and relu and residual is None and ops._scaled())
+        plan = ops._plan_forward(desc, split_w, relu, True, conv.bias is not None, fx["cb"], fx["virtual"], residual is not None, fr["virtual"],
+                                 fr["cb"], fr["half"], compact=ops._compact_now() or skip_y, single_piece_only=skip_y and not ops._compact_now(),
+                                 thin_ok=thin_ok, half=ops._half_now(),
+                                 no_cb=bool(shortcut_only and ops.SHORTCUT_NO_CB and not relu and residual is None and not ops._compact_now()))
+        ops._plan_backward(plan, desc, ops._use_split(desc.Cout), x.requires_grad, True, conv.bias is not None, fx["cb"], True)
+        y = torch.empty((desc.N, desc.Cout, desc.Ho, desc.Wo), device="meta", requires_grad=True)
+        y._facts = dict(cb=plan.want_cb, virtual=plan.compact, half=plan.half)
+        out.append((desc, plan, dict(res_virtual=fr["virtual"], need_x=x.requires_grad)))
+        return y
+    monkeypatch.setattr(ops, "conv_bn_act", group)
+    trunk = Trunk(*getattr(drn, net)(input_ch=6, num_classes=0).trunk()).train()
+    trunk(torch.empty((n, 6, h, w), device="meta"))
+    return out
+
+
+@pytest.mark.parametrize("net,shape", [("drn_d_38", (16, 480, 640)), ("drn_d_105", (32, 720, 1280))])
+@pytest.mark.parametrize("math,storage,half,max_bytes", [("f16x3", "fp32", True, None), ("f16x3", "compact", True, None), ("bf16x6", "fp32", True, None),
+                                                         ("f16x1", "compact", True, None), ("f16x1", "compact", False, None),
+                                                         ("f16x3", "fp32", True, 1 << 28)])
+def test_group_plan_invariants_of_every_layer(monkeypatch, net, shape, math, storage, half, max_bytes):
+    """``ops._plan_forward`` / ``ops._plan_backward`` -- the host decisions of a conv + BN + act group -- for every group of drn_d_38 at
+    BASELINE config 2 and of drn_d_105 at config 5, per arithmetic and storage form and once with batches cut: what the kernels a plan
+    selects require of each other holds for every plan.  Host arithmetic and the library's plan queries only."""
+    from mcdseg import ops
+    monkeypatch.setattr(ops, "CONV_MATH", math)
+    monkeypatch.setattr(ops, "ACT_STORAGE", storage)
+    monkeypatch.setattr(ops, "HALF_STORAGE", half)
+    if max_bytes is not None:
+        monkeypatch.setattr(ops, "MAX_CONV_BYTES", max_bytes)
+    groups = _walk_group_plans(monkeypatch, net, *shape)
+    assert len(groups) == {"drn_d_38": 38 - 1 + 4, "drn_d_105": 105 - 1 + 4}[net]  # every convolution but the head, + the projections
+    for desc, p, call in groups:
+        where = (net, math, storage, half, desc.Cin, desc.Cout, desc.KH, desc.H, p.storage, p.mask)
+        single = p.stem_tr or ops._uncut(desc) or desc.Cin > 16
+        # a group of the 2-byte chain: only in its arithmetic, and its weight gradient reads both companions
+        assert not p.half or (math == "f16x1" and half and storage == "compact" and p.wgrad_cb and ops._wgrad_reads_cb(desc)), where
+        # no fp32 dz: the data gradient (companion gather, whole batch or slices), the weight gradient and the bias allow it
+        assert not p.skip_dz or (p.use_cb and single and p.wgrad_cb and not p.has_bias), where
+        assert not p.wgrad_cb or (p.use_cb and single and (p.stem_tr or ops._wgrad_reads_cb(desc))), where
+        assert not p.x_fp32_bwd or not p.wgrad_cb, where
+        assert not p.compact or p.want_cb, where
+        # the bit-plane: a ReLU group with an fp32 residual; read in the backward pass only if the forward pass wrote one
+        assert not p.bits or (p.relu and p.has_res and not call["res_virtual"] and p.storage == "fp32"), where
+        assert p.mask != ops.MASK_BITS or (p.bits and p.use_cb), where
+        assert p.mask != ops.MASK_Z or (p.relu and not p.has_res), where
+        assert p.mask != ops.MASK_Y_CB or (p.compact and p.use_cb and p.relu), where
+        assert p.mask != ops.MASK_Y or not (p.compact and p.use_cb), where   # (no fp32 y exists there)
+        assert (p.mask == ops.MASK_NONE) == (not p.relu), where
+        assert not p.stem_tr or (desc.Cin % 8 != 0 and not call["need_x"]), where
+    plans = [p for _, p, _ in groups]
+    if math == "f16x1" and half:
+        assert sum(p.half for p in plans) >= len(plans) - 8  # all but the thin layers and the trunk's last stage
+    else:
+        assert not any(p.half for p in plans)
+    if storage == "fp32":
+        assert any(p.mask == ops.MASK_BITS for p in plans) and any(p.mask == ops.MASK_Z for p in plans)
+    if max_bytes is not None:
+        assert any(not ops._uncut(desc) for desc, _, _ in groups)

@@ -30,6 +30,6 @@ for c, h, w in ((16, 480, 640), (32, 240, 320), (64, 120, 160), (128, 60, 80), (
     z = torch.randn(n, c, h, w, device=dev)
     mean, rstd = torch.zeros(c, device=dev), torch.ones(c, device=dev)
     gamma, beta = torch.ones(c, device=dev), torch.zeros(c, device=dev)
-    t = timeit(lambda: ops._channel_reduce(dy, None, z, mean, rstd, True, gamma, want_bound=True, train=True, zmask_beta=beta))
+    t = timeit(lambda: ops._channel_reduce(dy, ops.MASK_Z, None, z, mean, rstd, gamma, beta, want_bound=True, train=True))
     nbytes = 2 * dy.numel() * 4
     print("reduce (zmask)  C=%4d %3dx%3d: %7.1f us  %6.0f GB/s  (%d MB)" % (c, h, w, t * 1e3, nbytes / t / 1e6, nbytes >> 20))
