@@ -22,6 +22,7 @@ import weakref
 
 import torch
 
+from . import _lib
 from ._lib import ConvDesc, check, get_option, lib
 
 # bumped by the optimizer after every in-place parameter update (the kernels write through raw
@@ -101,31 +102,24 @@ def _split_launches(d, presplit, dgrad, name, call, work=None):
     ``mcdseg_conv_split_parts`` gives to the ping-pong kernel (part 1) and the rest on the 4-wave tiles (part 2); ``call(part)``
     invokes the ``_part`` entry point.  Work is shared out by pixels."""
     if LAUNCH_TIMER is None:  # nobody asks which kernels ran: one call, the library launches both parts itself (and the host saves
-        call(0)               # the four plan queries below -- 700 convolutions per MCD step)
+        call(0)               # the plan queries below -- 700 convolutions per MCD step)
         return
-    if callable(name):
-        name = name()
+    def plan():  # the library's answers, asked once per (descriptor, arithmetic, presplit, dgrad): part 1's pixels and kernel, part 2's
+        L, r, m, g = lib(), ctypes.byref(d), MATH_ID[CONV_MATH], int(dgrad)
+        pp = L.mcdseg_conv_split_parts(r, m, 1, g) if presplit else 0
+        first = pingpong_kernel_name(dgrad, wide=L.mcdseg_conv_split_wide_pingpong(r, m, 1, g), deep=bool(L.mcdseg_conv_split_pp_deep(r, m, g))) \
+            if pp > 0 else None
+        rest = presplit and pp < pixels and L.mcdseg_conv_split_rest_pingpong(r, m, 1, g)
+        return pp, first, pingpong_kernel_name(dgrad, small=True) if rest else None
     pixels = d.N * (d.H * d.W if dgrad else d.Ho * d.Wo)
-    pp = lib().mcdseg_conv_split_parts(ctypes.byref(d), MATH_ID[CONV_MATH], int(presplit), int(dgrad)) if presplit else 0
+    pp, first, rest = _memo(d, ("split", bool(presplit), bool(dgrad)), plan)
     flops, byts = (work or conv_work)(d)
     if pp > 0:
-        wide = lib().mcdseg_conv_split_wide_pingpong(ctypes.byref(d), MATH_ID[CONV_MATH], 1, int(dgrad))
-        deep = bool(lib().mcdseg_conv_split_pp_deep(ctypes.byref(d), MATH_ID[CONV_MATH], int(dgrad)))
-        with _timed(pingpong_kernel_name(dgrad, wide=wide, deep=deep), (flops * pp / pixels, byts * pp / pixels)):
+        with _timed(first, (flops * pp / pixels, byts * pp / pixels)):
             call(1)
     if pp < pixels:
-        if presplit and lib().mcdseg_conv_split_rest_pingpong(ctypes.byref(d), MATH_ID[CONV_MATH], 1, int(dgrad)):
-            name = pingpong_kernel_name(dgrad, small=True)
-        with _timed(name, (flops * (pixels - pp) / pixels, byts * (pixels - pp) / pixels)):
+        with _timed(rest or (name() if callable(name) else name), (flops * (pixels - pp) / pixels, byts * (pixels - pp) / pixels)):
             call(2 if pp > 0 else 0)
-
-
-def wgrad_kernel_name(cout, cin, taps=9):
-    if cin <= 16 and taps > 1:
-        return "conv_wgrad_thin_kernel<%d, %s>" % (8 if cin <= 8 else 16, "true" if cout <= 16 else "false")
-    lo = min(cout, cin)
-    mid = lo > 32 or (lo > 16 and cin % 8 == 0 and cout % 8 == 0)  # (make_plan of csrc/conv_wgrad.hip: the 64 x 64 plan)
-    return "conv_wgrad_kernel<%s>" % ("2, 2, 2, 2, 16" if lo > 64 else ("1, 1, 2, 2, 32" if mid else "1, 1, 1, 1, 32"))
 
 
 def _p(t):
@@ -566,90 +560,95 @@ def _cb_slice(cb, a, channels, hw):
     return None if cb is None else ctypes.c_void_p(cb.data_ptr() + a * (channels // 8) * hw * 16)
 
 
-_PIECES_CACHE = {}
-
-
-def _batch_pieces(desc, wgrad_cb=None):
-    """[(first image, end)] of the launches a convolution's batch is cut into.  ``wgrad_cb``: None for the forward pass and the data
-    gradient; for the weight gradient, whether both pre-split companions will be passed.  (Memoised: a group asks several times per pass,
-    and the weight gradient's rule queries the library.)"""
-    from . import _lib
-    key = (desc.N, desc.Cin, desc.H, desc.W, desc.Cout, desc.KH, desc.KW, desc.stride, desc.pad, desc.dil, wgrad_cb, MAX_CONV_BYTES, CONV_MATH,
-           _lib.OPTION_EPOCH)
-    hit = _PIECES_CACHE.get(key)
-    if hit is None:
-        if len(_PIECES_CACHE) > 4096:
-            _PIECES_CACHE.clear()
-        hit = _PIECES_CACHE[key] = _batch_pieces_uncached(desc, wgrad_cb)
-    return hit
-
-
-def _batch_pieces_uncached(desc, wgrad_cb=None):
-    # the f32 kernels express padding and ragged channel tails as offsets the buffer range check rejects, up to a 128-channel tile
-    # past the tensor: (N*C + 128) * H*W * 4 < 2 GiB per operand -- the tile of slack is per LAUNCH, not per image (charging it per
-    # image cut the full-resolution 16-channel layers in two and lost their pre-split operands).  The split kernels mark such
-    # accesses with an explicit out-of-range offset instead, so the forward pass and the data gradient of a layer that runs on them
-    # (both channel counts multiples of 8, at least 16) need no slack: BASELINE config 5's 16- and 32-channel layers at
-    # 32 x 720 x 1280 (1.89 GB per tensor) stay in one launch and keep their companions.  The WEIGHT gradient is slack-free only on
-    # the plans that read both companions (mcdseg_conv_wgrad_fits states the library's own rule): the f32 plans of thin layers, the
-    # split plan without companions and bf16x6's thin layers still gather fp32 values with the slack.
-    if wgrad_cb and CONV_MATH in MATH_ID and desc.Cin <= 16:
-        # the thin layers' window weight gradient (csrc/conv_wgrad_thin_tr.hip) reads both companions of the WHOLE batch through one
-        # descriptor each and nothing else: the library's own rule decides (round 6: the stem at BASELINE config 5's N = 32 -- a 1.9 GB dz,
-        # two 0.9 GB pieces of its companion -- was cut by the fp32 kernels' slack rule and fell back to the f32 tap-packed kernel: 37 ms)
-        m = MATH_ID[CONV_MATH]
-        if lib().mcdseg_conv_wgrad_variant(ctypes.byref(desc), m, 1) == 15 and lib().mcdseg_conv_wgrad_fits(ctypes.byref(desc), m, 1):
-            return [(0, desc.N)]
-    split_only = CONV_MATH in MATH_ID and desc.Cin % 8 == 0 and desc.Cout % 8 == 0 and min(desc.Cin, desc.Cout) >= 16
-    if wgrad_cb is not None:
-        math = MATH_ID.get(CONV_MATH, 0)
-        split_only = split_only and bool(wgrad_cb) and lib().mcdseg_conv_wgrad_variant(ctypes.byref(desc), math, 1) >= 11
-    slack = 0 if split_only else 128
-    step = desc.N
-    for c, hw in ((desc.Cin, desc.H * desc.W), (desc.Cout, desc.Ho * desc.Wo)):
-        step = min(step, max(1, (MAX_CONV_BYTES - 4 * slack * hw) // (4 * c * hw)))
-    if wgrad_cb is not None:  # (the variant can change with N: hold every piece to the library's rule)
-        while step > 1 and not lib().mcdseg_conv_wgrad_fits(ctypes.byref(_sub_desc(desc, step, desc.N if wgrad_cb else 0)), math, int(wgrad_cb)):
-            step -= 1
-    if step >= desc.N:
-        return [(0, desc.N)]
-    return [(i, min(i + step, desc.N)) for i in range(0, desc.N, step)]
-
-
-def _conv_fprop(desc, x, wf, bias, want_stats, mpf, x_cb=None, x_bound=None, w_bound=None):
-    L = lib()
-    y = torch.empty((desc.N, desc.Cout, desc.Ho, desc.Wo), dtype=torch.float32, device=x.device)
-    pieces = _batch_pieces(desc)
-    # a batch cut along N keeps its companion: piece p of a slice lies p * N * (C/8) * HW * 16 bytes behind its piece 0 (Ncb)
-    descs = [desc if len(pieces) == 1 else _sub_desc(desc, b - a, desc.N if x_cb is not None else 0) for a, b in pieces]
-    split = _is_split(wf)
-    part, rows, row_off = None, 0, [0]
-    if want_stats:
-        for d in descs:
-            row_off.append(row_off[-1] + (L.mcdseg_conv_split_stat_rows_for(ctypes.byref(d), MATH_ID[CONV_MATH], int(x_cb is not None))
-                                          if split else L.mcdseg_conv_stat_rows(ctypes.byref(d))))
-        rows = row_off[-1]
-        part = torch.empty(rows * 3 * mpf, dtype=torch.float32, device=x.device)
-    direct = split and bool(L.mcdseg_conv_split_direct_ok(ctypes.byref(desc)))
-    if split and not direct:
-        x_bound = _bound_or_measure(x, x_bound)
-    for i, ((a, b), d) in enumerate(zip(pieces, descs)):
-        pp = None if part is None else ctypes.c_void_p(part.data_ptr() + 4 * row_off[i] * 3 * mpf)
-        def name(d=d):  # (formed only when a launch timer asks: it costs two queries of the library's plan)
-            return (_window_name(d, x_cb is not None, False) if split else None) \
-                or gemm_kernel_name(desc.Cout, desc.Cin, False, split, x_cb is not None, direct, d.N * d.Ho * d.Wo)
-        if split:
-            _split_launches(d, x_cb is not None, False, name, lambda part: check(L.mcdseg_conv_split_fprop_part(
-                ctypes.byref(d), MATH_ID[CONV_MATH], _p(_sl(x, a, b)), _cb_slice(x_cb, a, desc.Cin, desc.H * desc.W), _p(x_bound), _p(wf),
-                _p(w_bound), _p(bias), _p(y[a:b]), pp, part, _stream()), "conv_split_fprop"))
-        else:
-            with _timed(name() if LAUNCH_TIMER is not None else "", conv_work(d)):
-                check(L.mcdseg_conv_fprop(ctypes.byref(d), _p(x[a:b]), _p(wf), _p(bias), _p(y[a:b]), pp, _stream()), "conv_fprop")
-    return y, part, rows
+def _unit_slice(t, a, channels, hw):
+    """pointer to image ``a`` of a 16-bit tensor in the unit layout [N][C/8][HW][8]"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr() + a * channels * hw * 2)
 
 
 def _sl(t, a, b):
     return None if t is None else t[a:b]
+
+
+def _launches(desc, pieces, whole_cb):
+    """(first image, end, descriptor) of every launch of a convolution whose batch is cut into ``pieces``.  An uncut batch goes through on
+    ``desc`` itself.  ``whole_cb``: the companions passed along were written for the whole batch -- a slice keeps them: piece p of a slice
+    lies p * N * (C/8) * HW * 16 bytes behind its piece 0, which the kernels learn from Ncb"""
+    for a, b in pieces:
+        yield a, b, (desc if (a, b) == (0, desc.N) else _sub_desc(desc, b - a, desc.N if whole_cb else 0))
+
+
+_PLAN_CACHE = {}
+
+
+def _memo(desc, what, compute):
+    """``compute()``, once per geometry, question, MAX_CONV_BYTES, arithmetic and state of the library's options: a group asks for its
+    batch pieces and the library's plan answers several times per pass"""
+    key = (desc.N, desc.Cin, desc.H, desc.W, desc.Cout, desc.KH, desc.KW, desc.stride, desc.pad, desc.dil, desc.Ncb, MAX_CONV_BYTES, CONV_MATH,
+           _lib.OPTION_EPOCH) + what
+    hit = _PLAN_CACHE.get(key)
+    if hit is None:
+        if len(_PLAN_CACHE) > 4096:
+            _PLAN_CACHE.clear()
+        hit = _PLAN_CACHE[key] = compute()
+    return hit
+
+
+def _wgrad_variant(desc, have_cb, math=None):
+    """``mcdseg_conv_wgrad_variant``: the kernel the weight gradient of this geometry runs on -- 0..3 the f32 plans (128 / 64 / 32 tiles,
+    tap-packed thin), 10 and up the split-arithmetic plans, from 11 on those that read both pre-split companions and nothing else, 15 the
+    thin layers' window kernel.  ``math``: the active arithmetic, or 0 for what ``mcdseg_conv_wgrad`` launches."""
+    math = MATH_ID.get(CONV_MATH, 0) if math is None else math
+    return _memo(desc, ("wgrad", math, bool(have_cb)), lambda: lib().mcdseg_conv_wgrad_variant(ctypes.byref(desc), math, int(bool(have_cb))))
+
+
+def _cut(desc, elem_bytes, slack, fits=None):
+    """[(first image, end)]: the batch in the fewest equal launches whose operands -- ``elem_bytes`` per element, ``slack`` channels past the
+    tensor -- stay below MAX_CONV_BYTES and whose image count ``fits``"""
+    step = desc.N
+    for c, hw in ((desc.Cin, desc.H * desc.W), (desc.Cout, desc.Ho * desc.Wo)):
+        step = min(step, max(1, (MAX_CONV_BYTES - elem_bytes * slack * hw) // (elem_bytes * c * hw)))
+    while fits is not None and step > 1 and not fits(step):
+        step -= 1
+    return [(i, min(i + step, desc.N)) for i in range(0, desc.N, step)]
+
+
+def _batch_pieces(desc, wgrad_cb=None):
+    """[(first image, end)] of the launches a convolution's batch is cut into.  ``wgrad_cb``: None for the forward pass and the data
+    gradient; for the weight gradient, whether both pre-split companions will be passed."""
+    def pieces():
+        # the f32 kernels express padding and ragged channel tails as offsets the buffer range check rejects, up to a 128-channel tile
+        # past the tensor: (N*C + 128) * H*W * 4 < 2 GiB per operand -- the tile of slack is per LAUNCH, not per image (charging it per
+        # image cut the full-resolution 16-channel layers in two and lost their pre-split operands).  The split kernels mark such
+        # accesses with an explicit out-of-range offset instead, so the forward pass and the data gradient of a layer that runs on them
+        # (both channel counts multiples of 8, at least 16) need no slack: BASELINE config 5's 16- and 32-channel layers at
+        # 32 x 720 x 1280 (1.89 GB per tensor) stay in one launch and keep their companions.  The WEIGHT gradient is slack-free only on
+        # the plans that read both companions (mcdseg_conv_wgrad_fits states the library's own rule): the f32 plans of thin layers, the
+        # split plan without companions and bf16x6's thin layers still gather fp32 values with the slack.
+        math = MATH_ID.get(CONV_MATH, 0)
+        variant = _wgrad_variant(desc, True) if wgrad_cb else 0
+        # the thin layers' window weight gradient (csrc/conv_wgrad_thin_tr.hip) reads both companions of the WHOLE batch through one
+        # descriptor each and nothing else: the library's own rule decides (round 6: the stem at BASELINE config 5's N = 32 -- a 1.9 GB dz,
+        # two 0.9 GB pieces of its companion -- was cut by the fp32 kernels' slack rule and fell back to the f32 tap-packed kernel: 37 ms)
+        if variant == 15 and lib().mcdseg_conv_wgrad_fits(ctypes.byref(desc), math, 1):
+            return [(0, desc.N)]
+        split_only = bool(math) and desc.Cin % 8 == 0 and desc.Cout % 8 == 0 and min(desc.Cin, desc.Cout) >= 16
+        if wgrad_cb is None:
+            return _cut(desc, 4, 0 if split_only else 128)
+        return _cut(desc, 4, 0 if split_only and variant >= 11 else 128, lambda n: lib().mcdseg_conv_wgrad_fits(  # (the variant can change with N)
+            ctypes.byref(_sub_desc(desc, n, desc.N if wgrad_cb else 0)), math, int(wgrad_cb)))
+    return _memo(desc, ("pieces", wgrad_cb), pieces)
+
+
+def _batch_pieces_half(desc):
+    """[(first image, end)] of the launches of a convolution of the 2-byte chain: a launch addresses one piece of its pre-split operand
+    through a 32-bit buffer resource (< 2 GiB, 2 bytes per element); the 16-bit output is addressed with 64-bit pointers"""
+    return _cut(desc, 2, 0)
+
+
+def half_conv_work(d):
+    """(algorithmic FLOPs, algorithmic bytes) of one conv pass of the 2-byte chain: 16-bit operand in, 16-bit result out"""
+    flops, byts = conv_work(d)
+    return flops, byts // 2
 
 
 def _window_name(d, presplit, dgrad):
@@ -661,100 +660,98 @@ def _window_name(d, presplit, dgrad):
     return "conv_thin_window_kernel<%d, %d, %d, %s>" % (1 if stem else 2, m // 16, 13 if stem else 5, "true" if dgrad else "false")
 
 
-def _conv_dgrad(desc, dy, wd, dy_cb=None, dy_bound=None, w_bound=None, addend=None):
-    """``dy`` may be None when its pre-split companion is given and the batch is not cut (the kernel reads only ``dy_cb``).
-    ``addend``: another gradient of the same input (``GradBox``); the result is data gradient + addend -- in the kernel's epilogue
-    where the kernel can (``mcdseg_conv_split_dgrad_add``), by an element-wise add otherwise: the same bits either way."""
+def _fprop(desc, x, x_cb, x_bound, wf, w_bound, bias, want_stats, mpf, half):
+    """The forward convolution, fp32 result or -- ``half`` -- the 2-byte chain's (16-bit units from the companion alone): per launch the
+    entry point, the slice of the output and of the BatchNorm partial rows, and the kernel name a launch timer is given"""
     L = lib()
-    if addend is not None:
-        addend = _req(addend, "gradient addend")
-    dx = torch.empty((desc.N, desc.Cin, desc.H, desc.W), dtype=torch.float32, device=(dy if dy is not None else dy_cb).device)
-    pieces = _batch_pieces(desc)
-    split = _is_split(wd)
-    if split and dy is not None:
-        dy_bound = _bound_or_measure(dy, dy_bound)
-    for a, b in pieces:
-        d = desc if (a, b) == (0, desc.N) else _sub_desc(desc, b - a, desc.N if dy_cb is not None else 0)
-        def name(d=d):
-            return (_window_name(d, dy_cb is not None, True) if split else None) \
-                or gemm_kernel_name(desc.Cin, desc.Cout, True, split, dy_cb is not None, False, d.N * d.H * d.W)
-        if split and addend is not None and _window_name(d, dy_cb is not None, True) is None:
-            _split_launches(d, dy_cb is not None, True, name, lambda part: check(L.mcdseg_conv_split_dgrad_add(
-                ctypes.byref(d), MATH_ID[CONV_MATH], _p(_sl(dy, a, b)), _cb_slice(dy_cb, a, desc.Cout, desc.Ho * desc.Wo), _p(dy_bound),
-                _p(wd), _p(w_bound), _p(addend[a:b]), _p(dx[a:b]), part, _stream()), "conv_split_dgrad_add"))
-            continue
-        if split:
-            _split_launches(d, dy_cb is not None, True, name, lambda part: check(L.mcdseg_conv_split_dgrad_part(
-                ctypes.byref(d), MATH_ID[CONV_MATH], _p(_sl(dy, a, b)), _cb_slice(dy_cb, a, desc.Cout, desc.Ho * desc.Wo), _p(dy_bound),
-                _p(wd), _p(w_bound), _p(dx[a:b]), part, _stream()), "conv_split_dgrad"))
+    dev, hw_out = (x if x is not None else x_cb).device, desc.Ho * desc.Wo
+    presplit, split = x_cb is not None, half or _is_split(wf)
+    launches = list(_launches(desc, _batch_pieces_half(desc) if half else _batch_pieces(desc), presplit))
+    y = torch.empty(desc.N * desc.Cout * hw_out, dtype=torch.int16, device=dev) if half \
+        else torch.empty((desc.N, desc.Cout, desc.Ho, desc.Wo), dtype=torch.float32, device=dev)
+    y_bound = torch.empty(1, dtype=torch.float32, device=dev) if half else None
+    row_off = [0]  # BatchNorm partial rows: those of the launches, one behind the other
+    for _, _, d in launches if want_stats else ():
+        row_off.append(row_off[-1] + (L.mcdseg_conv_split_stat_rows_for(ctypes.byref(d), MATH_ID[CONV_MATH], int(presplit))
+                                      if split else L.mcdseg_conv_stat_rows(ctypes.byref(d))))
+    rows = row_off[-1]
+    part = torch.empty(rows * 3 * mpf, dtype=torch.float32, device=dev) if want_stats else None
+    direct = split and not half and bool(L.mcdseg_conv_split_direct_ok(ctypes.byref(desc)))
+    if split and not direct and not half:
+        x_bound = _bound_or_measure(x, x_bound)
+    for i, (a, b, d) in enumerate(launches):
+        pp = None if part is None else ctypes.c_void_p(part.data_ptr() + 4 * row_off[i] * 3 * mpf)
+        xs = _cb_slice(x_cb, a, desc.Cin, desc.H * desc.W)
+        def name():  # (formed only when a launch timer asks: it costs queries of the library's plan)
+            return (_window_name(d, presplit, False) if split and not half else None) \
+                or gemm_kernel_name(desc.Cout, desc.Cin, False, split, presplit, direct, d.N * hw_out)
+        if half:
+            _split_launches(d, True, False, name, lambda part_no: check(L.mcdseg_conv_split_fprop_half(
+                ctypes.byref(d), MATH_ID[CONV_MATH], xs, _p(x_bound), _p(wf), _p(w_bound), _unit_slice(y, a, desc.Cout, hw_out), _p(y_bound),
+                pp, part_no, _stream()), "conv_split_fprop_half"), half_conv_work)
+        elif split:
+            _split_launches(d, presplit, False, name, lambda part_no: check(L.mcdseg_conv_split_fprop_part(
+                ctypes.byref(d), MATH_ID[CONV_MATH], _p(_sl(x, a, b)), xs, _p(x_bound), _p(wf), _p(w_bound), _p(bias), _p(y[a:b]), pp, part_no,
+                _stream()), "conv_split_fprop"))
         else:
             with _timed(name() if LAUNCH_TIMER is not None else "", conv_work(d)):
-                check(L.mcdseg_conv_dgrad(ctypes.byref(d), _p(dy[a:b]), _p(wd), _p(dx[a:b]), _stream()), "conv_dgrad")
-        if addend is not None:
-            dx[a:b].add_(addend[a:b])
-    return dx
+                check(L.mcdseg_conv_fprop(ctypes.byref(d), _p(x[a:b]), _p(wf), _p(bias), _p(y[a:b]), pp, _stream()), "conv_fprop")
+    return (y, y_bound, part, rows) if half else (y, part, rows)
 
 
-def _batch_pieces_half(desc):
-    """[(first image, end)] of the launches of a convolution of the 2-byte chain: a launch addresses one piece of its pre-split operand
-    through a 32-bit buffer resource (< 2 GiB, 2 bytes per element); the 16-bit output is addressed with 64-bit pointers"""
-    step = desc.N
-    for c, hw in ((desc.Cin, desc.H * desc.W), (desc.Cout, desc.Ho * desc.Wo)):
-        step = min(step, max(1, MAX_CONV_BYTES // (2 * c * hw)))
-    if step >= desc.N:
-        return [(0, desc.N)]
-    return [(i, min(i + step, desc.N)) for i in range(0, desc.N, step)]
-
-
-def half_conv_work(d):
-    """(algorithmic FLOPs, algorithmic bytes) of one conv pass of the 2-byte chain: 16-bit operand in, 16-bit result out"""
-    flops, byts = conv_work(d)
-    return flops, byts // 2
-
-
-def _unit_slice(t, a, channels, hw):
-    """pointer to image ``a`` of a 16-bit tensor in the unit layout [N][C/8][HW][8]"""
-    return None if t is None else ctypes.c_void_p(t.data_ptr() + a * channels * hw * 2)
+def _conv_fprop(desc, x, wf, bias, want_stats, mpf, x_cb=None, x_bound=None, w_bound=None):
+    return _fprop(desc, x, x_cb, x_bound, wf, w_bound, bias, want_stats, mpf, False)
 
 
 def _conv_fprop_half(desc, x_cb, x_bound, wf, w_bound, mpf):
     """forward convolution of the 2-byte chain: (z16 units [int16], z_bound scalar, BatchNorm partial rows, row count)"""
+    return _fprop(desc, None, x_cb, x_bound, wf, w_bound, None, True, mpf, True)
+
+
+def _dgrad(desc, dy, dy_cb, dy_bound, wd, w_bound, addend, half):
+    """The data gradient (+ ``addend``), fp32 or -- ``half`` -- the 2-byte chain's bf16 units: per launch the entry point and the kernel
+    name a launch timer is given.  The sum is formed in the kernel's epilogue where the kernel can (``mcdseg_conv_split_dgrad_add``, the
+    chain's entry point), by an element-wise add otherwise: the same bits either way."""
     L = lib()
-    dev = x_cb.device
-    z16 = torch.empty(desc.N * desc.Cout * desc.Ho * desc.Wo, dtype=torch.int16, device=dev)
-    z_bound = torch.empty(1, dtype=torch.float32, device=dev)
-    pieces = _batch_pieces_half(desc)
-    descs = [desc if len(pieces) == 1 else _sub_desc(desc, b - a, desc.N) for a, b in pieces]
-    row_off = [0]
-    for d in descs:
-        row_off.append(row_off[-1] + L.mcdseg_conv_split_stat_rows_for(ctypes.byref(d), MATH_ID[CONV_MATH], 1))
-    rows = row_off[-1]
-    part = torch.empty(rows * 3 * mpf, dtype=torch.float32, device=dev)
-    for i, ((a, b), d) in enumerate(zip(pieces, descs)):
-        pp = ctypes.c_void_p(part.data_ptr() + 4 * row_off[i] * 3 * mpf)
-        def name(d=d):
-            return gemm_kernel_name(desc.Cout, desc.Cin, False, True, True, False, d.N * d.Ho * d.Wo)
-        _split_launches(d, True, False, name, lambda part_no: check(L.mcdseg_conv_split_fprop_half(
-            ctypes.byref(d), MATH_ID[CONV_MATH], _cb_slice(x_cb, a, desc.Cin, desc.H * desc.W), _p(x_bound), _p(wf), _p(w_bound),
-            _unit_slice(z16, a, desc.Cout, desc.Ho * desc.Wo), _p(z_bound), pp, part_no, _stream()), "conv_split_fprop_half"), work=half_conv_work)
-    return z16, z_bound, part, rows
+    addend = _req(addend, "gradient addend", torch.bfloat16 if half else torch.float32)
+    dx = torch.empty((desc.N, desc.Cin, desc.H, desc.W), dtype=torch.bfloat16 if half else torch.float32,
+                     device=(dy if dy is not None else dy_cb).device)
+    presplit, split = dy_cb is not None, half or _is_split(wd)
+    if split and dy is not None:
+        dy_bound = _bound_or_measure(dy, dy_bound)
+    for a, b, d in _launches(desc, _batch_pieces_half(desc) if half else _batch_pieces(desc), presplit):
+        ys = _cb_slice(dy_cb, a, desc.Cout, desc.Ho * desc.Wo)
+        # the LDS-window kernel has no adding epilogue: asked once, for the entry point and for the name
+        window = _window_name(d, presplit, True) if split and not half and (addend is not None or LAUNCH_TIMER is not None) else None
+        def name():
+            return window or gemm_kernel_name(desc.Cin, desc.Cout, True, split, presplit, False, d.N * d.H * d.W)
+        fused_add = addend is not None and split and window is None
+        if half:
+            _split_launches(d, True, True, name, lambda part_no: check(L.mcdseg_conv_split_dgrad_half(
+                ctypes.byref(d), MATH_ID[CONV_MATH], ys, _p(dy_bound), _p(wd), _p(w_bound), _unit_slice(addend, a, desc.Cin, desc.H * desc.W),
+                _unit_slice(dx, a, desc.Cin, desc.H * desc.W), part_no, _stream()), "conv_split_dgrad_half"), half_conv_work)
+        elif split:
+            entry, sum_with = (L.mcdseg_conv_split_dgrad_add, (_p(addend[a:b]),)) if fused_add else (L.mcdseg_conv_split_dgrad_part, ())
+            _split_launches(d, presplit, True, name, lambda part_no: check(entry(
+                ctypes.byref(d), MATH_ID[CONV_MATH], _p(_sl(dy, a, b)), ys, _p(dy_bound), _p(wd), _p(w_bound), *sum_with, _p(dx[a:b]), part_no,
+                _stream()), "conv_split_dgrad_add" if fused_add else "conv_split_dgrad"))
+        else:
+            with _timed(name() if LAUNCH_TIMER is not None else "", conv_work(d)):
+                check(L.mcdseg_conv_dgrad(ctypes.byref(d), _p(dy[a:b]), _p(wd), _p(dx[a:b]), _stream()), "conv_dgrad")
+        if addend is not None and not fused_add:
+            dx[a:b].add_(addend[a:b])
+    return dx
+
+
+def _conv_dgrad(desc, dy, wd, dy_cb=None, dy_bound=None, w_bound=None, addend=None):
+    """``dy`` may be None when its pre-split companion is given and the batch is not cut (the kernel reads only ``dy_cb``).
+    ``addend``: another gradient of the same input (``GradBox``); the result is data gradient + addend"""
+    return _dgrad(desc, dy, dy_cb, dy_bound, wd, w_bound, addend, False)
 
 
 def _conv_dgrad_half(desc, dy_cb, dy_bound, wd, w_bound, addend16=None):
     """data gradient of the 2-byte chain: bf16 units (+ the other gradient of the same tensor, same layout, in the kernel's epilogue)"""
-    L = lib()
-    dx = torch.empty((desc.N, desc.Cin, desc.H, desc.W), dtype=torch.bfloat16, device=dy_cb.device)
-    if addend16 is not None:
-        addend16 = _req(addend16, "gradient addend", torch.bfloat16)
-    for a, b in _batch_pieces_half(desc):
-        d = desc if (a, b) == (0, desc.N) else _sub_desc(desc, b - a, desc.N)
-        def name(d=d):
-            return gemm_kernel_name(desc.Cin, desc.Cout, True, True, True, False, d.N * d.H * d.W)
-        _split_launches(d, True, True, name, lambda part_no: check(L.mcdseg_conv_split_dgrad_half(
-            ctypes.byref(d), MATH_ID[CONV_MATH], _cb_slice(dy_cb, a, desc.Cout, desc.Ho * desc.Wo), _p(dy_bound), _p(wd), _p(w_bound),
-            _unit_slice(addend16, a, desc.Cin, desc.H * desc.W), _unit_slice(dx, a, desc.Cin, desc.H * desc.W), part_no, _stream()),
-            "conv_split_dgrad_half"), work=half_conv_work)
-    return dx
+    return _dgrad(desc, None, dy_cb, dy_bound, wd, w_bound, addend16, True)
 
 
 def _cb_wanted(channels):
@@ -796,46 +793,55 @@ def split_companion_padded(x, bound=None):
     return cb, bound
 
 
-# mcdseg_conv_wgrad_variant code -> the kernel name rocprofv3 prints
-_WGRAD_NAMES = {10: "conv_wgrad_split_kernel<%s>", 11: "conv_wgrad_split_cb_kernel<%s>", 12: "conv_wgrad_split_tr_kernel<%s, 2, 2, 3>",
+# mcdseg_conv_wgrad_variant code -> the kernel name rocprofv3 prints (%s: the arithmetic's policy)
+_WGRAD_NAMES = {0: "conv_wgrad_kernel<2, 2, 2, 2, 16>", 1: "conv_wgrad_kernel<1, 1, 2, 2, 32>", 2: "conv_wgrad_kernel<1, 1, 1, 1, 32>",
+                10: "conv_wgrad_split_kernel<%s>", 11: "conv_wgrad_split_cb_kernel<%s>", 12: "conv_wgrad_split_tr_kernel<%s, 2, 2, 3>",
                 13: "conv_wgrad_split_tr_kernel<%s, 4, 2, 3>", 14: "conv_wgrad_split_tr64_kernel<%s>",
                 17: "conv_wgrad_split_pp_kernel<%s>", 18: "conv_wgrad_split_pp3_kernel<%s>"}
 
 
-def wgrad_split_kernel_name(d, have_cb):
-    """rocprofv3's name of the split-arithmetic weight-gradient kernel the library launches for this geometry"""
-    v = lib().mcdseg_conv_wgrad_variant(ctypes.byref(d), MATH_ID[CONV_MATH], int(have_cb))
+def _wgrad_name(d, v):
+    """rocprofv3's name of the weight-gradient kernel with variant code ``v`` on this geometry"""
+    if v == 3:   # the tap-packed f32 kernel of the thin layers: <padded input channels per tap, Cout <= 16>
+        return "conv_wgrad_thin_kernel<%d, %s>" % (8 if d.Cin <= 8 else 16, "true" if d.Cout <= 16 else "false")
     if v == 15:  # csrc/conv_wgrad_thin_tr.hip: <channel groups of the input, row tiles, column tiles, tile rows> (no policy argument)
         cfg = lib().mcdseg_conv_wgrad_thin_tr_config(ctypes.byref(d))  # (the library's own choice, not a restatement of it)
         return "conv_wgrad_thin_tr_kernel<%d, %d, %d, %d>" % (cfg // 1000000, cfg // 10000 % 100, cfg // 100 % 100, cfg % 100)
-    policy = POLICY[CONV_MATH]
-    if v == 17 and CONV_MATH == "f16x1" and get_option("WGRAD_PP_DEEP"):
-        policy = "SplitF16x1D"  # six logical stages (csrc/conv_wgrad_split_pp.hip)
-    return _WGRAD_NAMES.get(v, "conv_wgrad<%s>") % policy
+    deep = v == 17 and CONV_MATH == "f16x1" and get_option("WGRAD_PP_DEEP")  # six logical stages (csrc/conv_wgrad_split_pp.hip)
+    return _WGRAD_NAMES.get(v, "conv_wgrad<%s>").replace("%s", "SplitF16x1D" if deep else POLICY.get(CONV_MATH, ""))
+
+
+def wgrad_kernel_name(cout, cin, taps=9):
+    """rocprofv3's name of the f32 weight-gradient kernel ``mcdseg_conv_wgrad`` launches for these channel counts (the library's plan
+    goes by them and the tap count alone: asked with a one-pixel geometry)"""
+    d = conv_desc((1, cin, taps, 1), (cout, cin, taps, 1), 1, 0, 1)
+    return _wgrad_name(d, _wgrad_variant(d, False, math=0))
+
+
+def wgrad_split_kernel_name(d, have_cb):
+    """rocprofv3's name of the split-arithmetic weight-gradient kernel the library launches for this geometry"""
+    return _wgrad_name(d, _wgrad_variant(d, have_cb))
 
 
 def _wgrad_thin_tr(desc):
     """the thin-layer window kernel (csrc/conv_wgrad_thin_tr.hip) takes this geometry when both companions exist"""
-    return _scaled() and desc.Cin <= 16 and lib().mcdseg_conv_wgrad_variant(ctypes.byref(desc), MATH_ID[CONV_MATH], 1) == 15
+    return _wgrad_variant(desc, True) == 15
 
 
 def _wgrad_split_plan(desc, have_cb=False):
-    """a split-arithmetic plan of csrc/conv_wgrad.hip applies (else the f32 kernels run): the 128x128 plan for
-    min(Cin, Cout) > 64, and -- from both pre-split companions only, f16x3 -- the 64-channel tap-pair plan for 32 < min <= 64
-    and the window kernel of the thin 3x3 layers"""
-    if CONV_MATH not in MATH_ID:
-        return False
-    if desc.Cin <= 16 and desc.KH * desc.KW > 1:
-        return bool(have_cb and _wgrad_thin_tr(desc))
-    lo = min(desc.Cout, desc.Cin)
-    if lo > 64:
-        return True
-    return get_option("WGRAD_TR64") != 0 and have_cb and _scaled() and lo > 16 and desc.Cin % 8 == 0 and desc.Cout % 8 == 0
+    """a split-arithmetic plan of csrc/conv_wgrad.hip applies (else the f32 kernels run): the 128x128 plan for min(Cin, Cout) > 64, and -- from
+    both pre-split companions only, f16x3 -- the 64-channel tap-pair plan for 32 < min <= 64 and the window kernel of the thin 3x3 layers"""
+    return _wgrad_variant(desc, have_cb) >= 10
+
+
+def _wgrad_reads_cb(desc):
+    """the weight gradient has a plan that reads both pre-split companions and nothing else.  (The channel counts are the host's own rule: the
+    stem, 6 input channels, is on plan 15 too, but from the zero-PADDED companion that only ``_plan_backward``'s ``stem_tr`` provides.)"""
+    return _wgrad_variant(desc, True) >= 11 and desc.Cin % 8 == 0 and desc.Cout % 8 == 0
 
 
 def _conv_wgrad(desc, x, dy, x_cb=None, dy_cb=None, x_bound=None, dy_bound=None):
-    L = lib()
-    total = None
+    L, total = lib(), None
     if x_cb is None or dy_cb is None:
         x_cb = dy_cb = None  # both companions or none
     pieces = _batch_pieces(desc, wgrad_cb=x_cb is not None)
@@ -845,8 +851,7 @@ def _conv_wgrad(desc, x, dy, x_cb=None, dy_cb=None, x_bound=None, dy_bound=None)
     split = _wgrad_split_plan(desc, x_cb is not None)
     if split and x_cb is None:
         x_bound, dy_bound = _bound_or_measure(x, x_bound), _bound_or_measure(dy, dy_bound)
-    for a, b in pieces:
-        d = desc if (a, b) == (0, desc.N) else _sub_desc(desc, b - a, desc.N if x_cb is not None else 0)
+    for a, b, d in _launches(desc, pieces, x_cb is not None):
         ws = _ws(L.mcdseg_conv_wgrad_workspace_bytes(ctypes.byref(d)), (x if x is not None else x_cb).device)
         dw = torch.empty((desc.Cout, desc.Cin, desc.KH, desc.KW), dtype=torch.float32, device=ws.device)
         name = "" if LAUNCH_TIMER is None else (wgrad_split_kernel_name(d, x_cb is not None) if split else
@@ -1218,11 +1223,6 @@ def _uncut(desc, wgrad_cb=None):
     return len(_batch_pieces(desc, wgrad_cb)) == 1
 
 
-def _wgrad_reads_cb(desc):
-    """the weight gradient has a plan that reads both pre-split companions and nothing else"""
-    return bool(_wgrad_split_plan(desc, True)) and desc.Cin % 8 == 0 and desc.Cout % 8 == 0
-
-
 class _GroupPlan:
     """Every host decision of one conv + BN + act group, as plain values: it hangs on ``ctx`` and must keep no tensor alive.
     ``_plan_forward`` fills the first row of slots when the group is called, ``_plan_backward`` the second at the top of a backward pass."""
@@ -1517,8 +1517,7 @@ def _conv_bn_act_inference(x, conv, bn, relu, residual):
     split = _is_split(wf)
     direct = split and bool(L.mcdseg_conv_split_direct_ok(ctypes.byref(desc)))
     x_bound = _bound_or_measure(x, None) if (split and not direct) else None
-    for a, b in _batch_pieces(desc):
-        d = desc if (a, b) == (0, desc.N) else _sub_desc(desc, b - a)
+    for a, b, d in _launches(desc, _batch_pieces(desc), False):
         with _timed(gemm_kernel_name(desc.Cout, desc.Cin, False, split, False, direct), conv_work(d)):
             args = (_p(scale), _p(shift), _p(residual[a:b]) if residual is not None else None, int(relu), _p(y[a:b]), _stream())
             if split:

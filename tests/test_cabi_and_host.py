@@ -1,6 +1,7 @@
 """CPU: the C-ABI library loads and exports every symbol of include/mcdseg.h; host-side logic (flags, helpers,
 factory, checkpoint layout) behaves like the reference's.  No kernel is launched here."""
 import argparse
+import json
 import os
 import re
 
@@ -618,3 +619,23 @@ def test_group_plan_invariants_of_every_layer(monkeypatch, net, shape, math, sto
         assert any(p.mask == ops.MASK_BITS for p in plans) and any(p.mask == ops.MASK_Z for p in plans)
     if max_bytes is not None:
         assert any(not ops._uncut(desc) for desc, _, _ in groups)
+
+
+def test_conv_launch_table_of_every_layer(golden):
+    """tests/golden/conv_launch_table.json (make_conv_launch_table.py: taken before the launch drivers of mcdseg/ops.py were folded into
+    one) -- batch pieces, the weight gradient's plan predicates and kernel names, the forward and data-gradient kernel names with their
+    two-part split and work shares, for every convolution of drn_d_38 at BASELINE config 2 and drn_d_105 at config 5 under every
+    arithmetic, a forced cut and the weight-gradient options: every cell is recomputed and must equal the recorded one.  Host
+    arithmetic and the library's plan queries only."""
+    import make_conv_launch_table as table
+    from mcdseg import ops
+    t = golden.json("conv_launch_table.json")
+    assert t["settings"] == table.settings() and t["fields"] == list(table.FIELDS) and t["keys"] == list(table.KEYS)
+    assert len(t["table"]) == len(t["geometries"]) >= 80 and all(len(row) == len(t["settings"]) for row in t["table"])
+    for si, setting in enumerate(t["settings"]):
+        with table.applied(ops, setting):
+            for gi, g in enumerate(t["geometries"]):
+                got = json.loads(json.dumps(table.split_record(table.record(ops, table.make_desc(ops, g)))))
+                want = table.lookup(t, gi, si)
+                for key in t["keys"]:
+                    assert got[key] == want[key], (g, setting, key)
