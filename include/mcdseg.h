@@ -499,6 +499,18 @@ int mcdseg_unpack_bf16_units(const void* in16, float* x, int32_t N, int32_t C, i
 int mcdseg_sgd_momentum_flat(float* p, const float* g, float* v, int64_t n, float lr, float momentum,
                              float weight_decay, float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Adam with L2 weight decay on flat buffers (torch.optim.Adam via models/model_util.py:293-294: no amsgrad, no maximize,
+ * no decoupled decay).  The caller forms the bias corrections of step t in double precision and passes
+ * lr_over_bc1 = lr / (1 - beta1^t) and inv_sqrt_bc2 = 1 / sqrt(1 - beta2^t); the kernel reads no step counter.
+ *   d = g*grad_scale + wd*p ; m += (1-beta1)*(d - m) ; v = beta2*v + (1-beta2)*d*d     (m in the form of torch's lerp)
+ *   p -= lr_over_bc1 * m / (sqrt(v)*inv_sqrt_bc2 + eps)                                  (m and v start at 0)
+ * 1 - beta is formed in double precision from the decimal the float stands for when beta has at most six decimals
+ * (0.5, 0.9, 0.999, ...), from the float itself otherwise.  28 B per parameter.
+ * ---------------------------------------------------------------------------------------------- */
+int mcdseg_adam_flat(float* p, const float* g, float* m, float* v, int64_t n, float lr_over_bc1, float beta1, float beta2,
+                     float inv_sqrt_bc2, float eps, float weight_decay, float grad_scale, void* stream);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -57,7 +57,9 @@ def get_common_training_parser(parser):
     parser.add_argument("--net", type=str, default="drn_d_38", help="network structure", choices=AVAILABLE_NET_LIST)
     parser.add_argument("--res", type=str, default="50", metavar="ResnetLayerNum", choices=["18", "34", "50", "101", "152"])
     parser.add_argument("--is_data_parallel", action="store_true", help="wrap models so checkpoints carry the module. prefix")
-    parser.add_argument("--opt", type=str, default="sgd", choices=["sgd", "adam"], help="network optimizer")
+    parser.add_argument("--opt", type=str, default="sgd", choices=["sgd", "adam"],
+                        help="network optimizer: flat-buffer HIP SGD, or flat-buffer HIP Adam with betas (0.5, 0.999); both "
+                             "all-reduce their gradients under data parallelism")
     parser.add_argument("--lr", type=float, default=1e-3, help="learning rate (default: 0.001)")
     parser.add_argument("--adjust_lr", action="store_true", help="whether you change lr")
     parser.add_argument("--momentum", type=float, default=0.9, help="momentum sgd (default: 0.9)")

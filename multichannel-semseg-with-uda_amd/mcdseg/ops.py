@@ -2200,3 +2200,20 @@ def sgd_momentum_flat_(p, g, v, lr, momentum, weight_decay, grad_scale=1.0, para
         check(lib().mcdseg_sgd_momentum_flat(_p(p), _p(g), _p(v), p.numel(), float(lr), float(momentum), float(weight_decay),
                                              float(grad_scale), _stream()), "sgd_momentum_flat")
     bump_weight_epoch(params)
+
+
+def adam_flat_(p, g, m, v, lr, betas, eps, weight_decay, step, grad_scale=1.0, params=None):
+    """one Adam update (L2 weight decay, no amsgrad) of the flat buffers; ``step`` is the count of THIS update (1 for the first), whose
+    bias corrections are formed here in double precision.  ``params`` as for ``sgd_momentum_flat_``."""
+    for t, name in ((p, "params"), (g, "grads"), (m, "exp_avg"), (v, "exp_avg_sq")):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError("mcdseg: flat Adam needs contiguous fp32 GPU buffers (%s)" % name)
+    b1, b2 = float(betas[0]), float(betas[1])
+    step = int(step)
+    if step < 1:
+        raise ValueError("mcdseg: flat Adam's step count starts at 1, got %r" % (step,))
+    bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
+    with _timed("adam_kernel", (0, 28 * p.numel())):
+        check(lib().mcdseg_adam_flat(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr) / bc1, b1, b2, bc2 ** -0.5, float(eps),
+                                     float(weight_decay), float(grad_scale), _stream()), "adam_flat")
+    bump_weight_epoch(params)

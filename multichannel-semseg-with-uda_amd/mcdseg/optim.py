@@ -1,14 +1,19 @@
-"""Flat-buffer SGD (momentum + weight decay) driven by one HIP kernel per step.
+"""Flat-buffer optimizers, each driven by one HIP kernel per step: ``FlatSGD`` (momentum + weight decay) and ``FlatAdam``.
 
-Drop-in for ``torch.optim.SGD`` as the reference configures it (models/model_util.py:289-292:
-dampening 0, no Nesterov): same constructor arguments, ``param_groups``, ``zero_grad``, ``step`` and a
-``state_dict`` in torch's own layout (``state[i]['momentum_buffer']`` + ``param_groups``), so
-checkpoints interchange with the reference (adapt_trainer.py:232-245, 29-59).
+Drop-ins for ``torch.optim.SGD`` and ``torch.optim.Adam`` as the reference configures them (models/model_util.py:289-294:
+SGD with dampening 0 and no Nesterov; Adam with L2 weight decay, no amsgrad): same constructor arguments, ``param_groups``,
+``zero_grad``, ``step`` and a ``state_dict`` in torch's own layout (``state[i]['momentum_buffer']``, or
+``state[i]['step' | 'exp_avg' | 'exp_avg_sq']``, + ``param_groups``), so checkpoints interchange with the reference
+(adapt_trainer.py:232-245, 29-59).
 
 Parameters are re-homed, on first use, into one contiguous fp32 buffer (each ``p.data`` becomes a view
-of it); momentum lives in a second flat buffer and gradients are gathered into a third, which is also
-the single payload of the data-parallel all-reduce (``mcdseg.dist``).  Parameters whose ``grad`` is
-None are skipped exactly as torch does (no weight decay, no momentum update).
+of it); the optimizer's per-parameter state (momentum; Adam's two moments) lives in further flat buffers and gradients are
+gathered into another, which is also the single payload of the data-parallel all-reduce (``mcdseg.dist``).  Parameters whose
+``grad`` is None are skipped exactly as torch does (no weight decay, no state update, no step count).
+
+``_FlatOptimizer`` holds everything that does not depend on the update rule: the flat storage, the run detection, the all-reduce
+(whole, or bucketed during backward) and the state dict's way in and out of the flat buffers.  A subclass names its state buffers
+(``_STATE``), the hyper-parameters a run of parameters must share (``_run_key``) and the kernel call (``_update``).
 """
 import os
 
@@ -31,16 +36,20 @@ DP_OVERLAP = os.environ.get("MCDSEG_DP_OVERLAP", "0") == "1"
 DP_BUCKET_MB = float(os.environ.get("MCDSEG_DP_BUCKET_MB", "25"))
 
 
-class FlatSGD(torch.optim.Optimizer):
-    # The update kernel is HIP-only.  Tests of the host-side logic (flat layout, run detection, the gloo
+class _FlatOptimizer(torch.optim.Optimizer):
+    # The update kernels are HIP-only.  Tests of the host-side logic (flat layout, run detection, the gloo
     # all-reduce of the data-parallel path) clear this flag and substitute a reference update for the kernel.
     _require_gpu = True
+    # ((key of the flat buffer in ``_flat``, name of its per-parameter view in ``state[p]``), ...)
+    _STATE = ()
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
-        if lr < 0 or momentum < 0 or weight_decay < 0:
-            raise ValueError("FlatSGD: negative hyper-parameter")
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=0, nesterov=False))
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self._flat = None
+
+    @property
+    def _name(self):
+        return type(self).__name__
 
     # ------------------------------------------------------------------ flat storage
     def _all_params(self):
@@ -55,18 +64,18 @@ class FlatSGD(torch.optim.Optimizer):
     def _flatten(self):
         params = self._all_params()
         if not params:
-            raise ValueError("FlatSGD: no parameters")
+            raise ValueError("%s: no parameters" % self._name)
         dev = params[0].device
         if dev.type != "cuda" and self._require_gpu:
-            raise RuntimeError("FlatSGD: parameters must be on the GPU before the first step (no CPU fallback)")
+            raise RuntimeError("%s: parameters must be on the GPU before the first step (no CPU fallback)" % self._name)
         offs, total = [], 0
         for p in params:
             if p.device != dev or p.dtype != torch.float32:
-                raise RuntimeError("FlatSGD: all parameters must be fp32 on one device")
+                raise RuntimeError("%s: all parameters must be fp32 on one device" % self._name)
             offs.append(total)
             total += (p.numel() + _ALIGN - 1) // _ALIGN * _ALIGN
         fp = torch.zeros(total, dtype=torch.float32, device=dev)
-        fv = torch.zeros(total, dtype=torch.float32, device=dev)
+        fs = [torch.zeros(total, dtype=torch.float32, device=dev) for _ in self._STATE]
         fg = torch.zeros(total, dtype=torch.float32, device=dev)
         views = {}
         for p, o in zip(params, offs):
@@ -74,15 +83,31 @@ class FlatSGD(torch.optim.Optimizer):
             pv = fp[o:o + n].view(p.shape)
             pv.copy_(p.data)
             p.data = pv
-            vv = fv[o:o + n].view(p.shape)
-            st = self.state.get(p)
-            if st and st.get("momentum_buffer") is not None:
-                vv.copy_(st["momentum_buffer"])
-                st["momentum_buffer"] = vv
-            views[id(p)] = (o, n, vv, fg[o:o + n].view(p.shape))
-        self._flat = dict(p=fp, v=fv, g=fg, params=params, offs=offs, views=views, total=total)
+            sv = [f[o:o + n].view(p.shape) for f in fs]
+            # (offset, size, view of the first state buffer, view of the gradient buffer, views of the further state buffers ...)
+            views[id(p)] = (o, n, sv[0], fg[o:o + n].view(p.shape)) + tuple(sv[1:])
+        self._flat = dict(p=fp, g=fg, params=params, offs=offs, views=views, total=total)
+        self._flat.update((key, f) for (key, _), f in zip(self._STATE, fs))
+        self._adopt_state(fresh=True)
         ops.bump_weight_epoch()
         self._setup_overlap()
+
+    def _state_views(self, p):
+        t = self._flat["views"][id(p)]
+        return (t[2],) + t[4:]
+
+    def _adopt_state(self, fresh=False):
+        """move the state tensors that ``state`` holds (loaded from a checkpoint, or views of an earlier flat storage) into the flat
+        buffers; a parameter without one gets zeros there (``fresh``: has them already)"""
+        for p in self._flat["params"]:
+            st = self.state.get(p) or {}
+            for (_, name), view in zip(self._STATE, self._state_views(p)):
+                if st.get(name) is None:
+                    if not fresh:
+                        view.zero_()
+                elif st[name] is not view:
+                    view.copy_(st[name])
+                    st[name] = view
 
     # ------------------------------------------------------------------ bucketed all-reduce during backward (optional)
     def _setup_overlap(self):
@@ -249,7 +274,7 @@ class FlatSGD(torch.optim.Optimizer):
         # .cuda()/.to()/load_state_dict(assign) may have re-homed a parameter: rebuild if any view moved
         fl = self._flat
         for p in fl["params"]:
-            o, n, _, _ = fl["views"][id(p)]
+            o = fl["views"][id(p)][0]
             if p.data_ptr() != fl["p"].data_ptr() + 4 * o:
                 self._flat = None
                 self._flatten()
@@ -275,7 +300,7 @@ class FlatSGD(torch.optim.Optimizer):
             if p.grad is None:
                 cur = None
                 continue
-            key = (g["lr"], g["momentum"], g["weight_decay"])
+            key = self._run_key(g, p)
             if cur is None or cur["key"] != key:
                 cur = dict(key=key, params=[])
                 runs.append(cur)
@@ -294,11 +319,7 @@ class FlatSGD(torch.optim.Optimizer):
                 torch._foreach_copy_(gviews, grads)
                 if mdist.is_distributed():
                     mdist.all_reduce_sum_(gflat)
-            lr, mu, wd = run["key"]
-            ops.sgd_momentum_flat_(fl["p"][lo:hi], gflat, fl["v"][lo:hi], lr, mu, wd, 1.0 / world, params=ps)
-            if mu != 0:
-                for p in ps:
-                    self.state[p]["momentum_buffer"] = fl["views"][id(p)][2]
+            self._update(fl, lo, hi, gflat, run["key"], ps, 1.0 / world)
         self._reset_overlap()
         return loss
 
@@ -309,24 +330,86 @@ class FlatSGD(torch.optim.Optimizer):
 
     def state_dict(self):
         sd = super().state_dict()
-        for st in sd["state"].values():
-            if "momentum_buffer" in st and st["momentum_buffer"] is not None:
-                st["momentum_buffer"] = st["momentum_buffer"].clone()  # detach from the flat storage
+        # copies, detached from the flat storage (and from Adam's live step counters) -- in dicts of their own: torch hands out the
+        # optimizer's live per-parameter dicts
+        sd["state"] = {k: {name: (t.clone() if torch.is_tensor(t) else t) for name, t in st.items()} for k, st in sd["state"].items()}
         return sd
 
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
+        # torch keeps a tensor that needs no cast as the caller's own object, which the caller (another optimizer's live state, say) may go
+        # on changing: what stays outside the flat buffers -- Adam's step counters always, everything before the first step, when
+        # ``_flatten`` adopts what was loaded -- is copied here
+        names = {name for _, name in self._STATE}
+        for st in self.state.values():
+            st.update((name, t.clone()) for name, t in list(st.items()) if torch.is_tensor(t) and (name not in names or self._flat is None))
         if self._flat is not None:
-            fl = self._flat
-            fl["v"].zero_()
-            for p in fl["params"]:
-                st = self.state.get(p)
-                if st and st.get("momentum_buffer") is not None:
-                    vv = fl["views"][id(p)][2]
-                    vv.copy_(st["momentum_buffer"])
-                    st["momentum_buffer"] = vv
+            self._adopt_state()
+
+    def flat_buffers(self):
+        """(params, grads, state buffers in ``_STATE`` order ...) flat tensors -- for tests and the bench's byte accounting."""
+        self._ensure_flat()
+        return (self._flat["p"], self._flat["g"]) + tuple(self._flat[key] for key, _ in self._STATE)
+
+    # ------------------------------------------------------------------ what a subclass supplies
+    def _run_key(self, group, p):
+        """what consecutive parameters must share to be updated by one kernel launch (``p`` has a gradient)"""
+        raise NotImplementedError
+
+    def _update(self, fl, lo, hi, gflat, key, ps, grad_scale):
+        """update ``fl[...][lo:hi]`` -- the parameters ``ps``, one run -- from the (summed) gradients ``gflat``"""
+        raise NotImplementedError
+
+
+class FlatSGD(_FlatOptimizer):
+    _STATE = (("v", "momentum_buffer"),)
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
+        if lr < 0 or momentum < 0 or weight_decay < 0:
+            raise ValueError("FlatSGD: negative hyper-parameter")
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=0, nesterov=False))
+
+    def _run_key(self, group, p):
+        return (group["lr"], group["momentum"], group["weight_decay"])
+
+    def _update(self, fl, lo, hi, gflat, key, ps, grad_scale):
+        lr, mu, wd = key
+        ops.sgd_momentum_flat_(fl["p"][lo:hi], gflat, fl["v"][lo:hi], lr, mu, wd, grad_scale, params=ps)
+        if mu != 0:
+            for p in ps:
+                self.state[p]["momentum_buffer"] = fl["views"][id(p)][2]
 
     def flat_buffers(self):
         """(params, grads, momentum) flat tensors -- for tests and the bench's byte accounting."""
-        self._ensure_flat()
-        return self._flat["p"], self._flat["g"], self._flat["v"]
+        return super().flat_buffers()
+
+
+class FlatAdam(_FlatOptimizer):
+    """``torch.optim.Adam`` with L2 weight decay.  A parameter's ``state['step']`` counts the updates IT received (torch's layout: a
+    0-dim fp32 CPU tensor), so a parameter that went without a gradient falls behind its neighbours and starts a run of its own."""
+    _STATE = (("m", "exp_avg"), ("v", "exp_avg_sq"))
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, amsgrad=False, maximize=False):
+        if amsgrad or maximize:
+            raise NotImplementedError("FlatAdam: amsgrad and maximize are not implemented")
+        if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
+            raise ValueError("FlatAdam: negative hyper-parameter, or a beta outside [0, 1)")
+        # every key torch.optim.Adam writes into a group, so that a state dict loads either way
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False,
+                                      foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False))
+
+    def _run_key(self, group, p):
+        if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):  # (a loaded group may say so)
+            raise NotImplementedError("FlatAdam: amsgrad, maximize and decoupled weight decay are not implemented")
+        st = self.state[p]
+        if "step" not in st:
+            m, v = self._state_views(p)
+            st.update(step=torch.tensor(0.0, dtype=torch.float32), exp_avg=m, exp_avg_sq=v)
+        elif not torch.is_tensor(st["step"]):  # (checkpoints of old torch versions carry a plain number)
+            st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
+        return (float(group["lr"]), tuple(group["betas"]), group["eps"], group["weight_decay"], int(st["step"]) + 1)
+
+    def _update(self, fl, lo, hi, gflat, key, ps, grad_scale):
+        lr, betas, eps, wd, t = key
+        ops.adam_flat_(fl["p"][lo:hi], gflat, fl["m"][lo:hi], fl["v"][lo:hi], lr, betas, eps, wd, t, grad_scale, params=ps)
+        torch._foreach_add_([self.state[p]["step"] for p in ps], 1)

@@ -2,7 +2,10 @@
 
 Only the DRN branches -- the ones the MCD hot path uses -- are implemented; every other network name
 raises ``NotImplementedError`` (the reference's message is kept).  ``get_optimizer('sgd')`` returns the
-flat-buffer HIP SGD (``mcdseg.optim.FlatSGD``), state-dict compatible with ``torch.optim.SGD``.
+flat-buffer HIP SGD (``mcdseg.optim.FlatSGD``) and ``get_optimizer('adam')`` the flat-buffer HIP Adam
+(``mcdseg.optim.FlatAdam``, betas (0.5, 0.999) as in the reference), state-dict compatible with ``torch.optim.SGD`` /
+``torch.optim.Adam``; both sum their gradients over the ranks of a data-parallel run.  ``'adadelta'``, which the
+command line cannot select, stays on torch and is not data-parallel.
 """
 import os
 
@@ -91,7 +94,8 @@ def get_optimizer(model_parameters, opt, lr, momentum, weight_decay):
     elif opt == "adadelta":
         return torch.optim.Adadelta(params, lr=lr, weight_decay=weight_decay)
     elif opt == "adam":
-        return torch.optim.Adam(params, lr=lr, betas=[0.5, 0.999], weight_decay=weight_decay)
+        from mcdseg.optim import FlatAdam
+        return FlatAdam(params, lr=lr, betas=(0.5, 0.999), weight_decay=weight_decay)
     raise NotImplementedError("Only (Momentum) SGD, Adadelta, Adam are supported!")
 
 
