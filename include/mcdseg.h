@@ -407,7 +407,9 @@ int mcdseg_mse(const float* pred, const float* target, float* grad, float* loss,
 /* ------------------------------------------------------------------------------------------------
  * MFNet late fusion beyond the plain sum (models/fusion.py:6-50) and its loss (loss.py:16-30)
  *   gate_mix:    out = x1*s + x2*(1-s), s = sigmoid(g)   (GateFusion.forward :19-22; g = 1x1 conv of cat(x1,x2))
- *                backward: dx1 = dy*s, dx2 = dy*(1-s), dg = dy*(x1-x2)*s*(1-s).  n = element count, multiple of 4.
+ *                backward: dx1 = dy*s, dx2 = dy*(1-s), dg = dy*(x1-x2)*s*(1-s).  n = element count, any n > 0; pointers
+ *                need only float alignment (16-byte vector accesses are used when every pointer of the call allows them,
+ *                a scalar pass otherwise, with the same bits).
  *   softmax_ch:  softmax over C of NCHW (F.softmax of ScoreGateFusion :13-15); backward dx = y*(dy - sum_c dy*y). C <= 64.
  *   prob_nll:    ProbCrossEntropyLoss2d: NLLLoss2d(weight)(log(p), labels).  loss[0] = weighted mean, loss[1] = weighted
  *                sum, loss[2] = sum of weights; grad (may be NULL) = d loss[size_average ? 0 : 1] / dp, dense NCHW.

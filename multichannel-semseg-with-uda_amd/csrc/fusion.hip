@@ -3,6 +3,8 @@
 //
 //  gate_mix      out = x1*s + x2*(1-s),  s = sigmoid(g)                         (GateFusion.forward, fusion.py:19-22)
 //                dx1 = dy*s ; dx2 = dy*(1-s) ; dg = dy*(x1-x2)*s*(1-s)
+//                any element count > 0 and any 4-byte-aligned pointers: float4 body + scalar tail when every pointer of the
+//                call is 16-byte aligned, all scalar otherwise; the same bits either way
 //  softmax_ch    y = softmax over the channel axis of NCHW                      (F.softmax, fusion.py:13-15)
 //                dx = y*(dy - sum_c dy*y)
 //  prob_nll      loss = sum_i w[y_i]*(-log p[y_i]) / sum_i w[y_i]                (NLLLoss2d(log(p)), loss.py:30)
@@ -12,39 +14,65 @@
 namespace {
 
 
-__global__ __launch_bounds__(256) void gate_mix_fwd_kernel(const float4* __restrict__ x1, const float4* __restrict__ x2,
-                                                           const float4* __restrict__ g, float4* __restrict__ out, int64_t n4) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 a = x1[i], b = x2[i], gg = g[i];
-    float4 o;
-    float s;
-    s = 1.0f / (1.0f + expf(-gg.x)); o.x = a.x * s + b.x * (1.0f - s);
-    s = 1.0f / (1.0f + expf(-gg.y)); o.y = a.y * s + b.y * (1.0f - s);
-    s = 1.0f / (1.0f + expf(-gg.z)); o.z = a.z * s + b.z * (1.0f - s);
-    s = 1.0f / (1.0f + expf(-gg.w)); o.w = a.w * s + b.w * (1.0f - s);
-    out[i] = o;
-  }
+// float4 body over [0, 4*n4), scalar tail over [4*n4, n); n4 = 0 (all scalar) when a pointer is off the 16-byte grid.  Body and
+// tail evaluate one expression per element, so a value does not depend on which of the two computed it.
+__device__ __forceinline__ float gate_sigmoid(float g) { return 1.0f / (1.0f + expf(-g)); }
+__device__ __forceinline__ float gate_mix_one(float a, float b, float g) {
+  const float s = gate_sigmoid(g);
+  return a * s + b * (1.0f - s);
 }
 
-__global__ __launch_bounds__(256) void gate_mix_bwd_kernel(const float4* __restrict__ dy, const float4* __restrict__ x1,
-                                                           const float4* __restrict__ x2, const float4* __restrict__ g,
-                                                           float4* __restrict__ dx1, float4* __restrict__ dx2,
-                                                           float4* __restrict__ dg, int64_t n4) {
+__global__ __launch_bounds__(256) void gate_mix_fwd_kernel(const float* __restrict__ x1, const float* __restrict__ x2,
+                                                           const float* __restrict__ g, float* __restrict__ out, int64_t n4,
+                                                           int64_t n) {
+  const float4* a4 = reinterpret_cast<const float4*>(x1);
+  const float4* b4 = reinterpret_cast<const float4*>(x2);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* o4 = reinterpret_cast<float4*>(out);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-    const float4 d = dy[i], a = x1[i], b = x2[i], gg = g[i];
-    float4 o1, o2, og;
-    float s;
-#define MCD_GATE_LANE(f)                         \
-    s = 1.0f / (1.0f + expf(-gg.f));             \
-    o1.f = d.f * s;                              \
-    o2.f = d.f * (1.0f - s);                     \
-    og.f = d.f * (a.f - b.f) * (s * (1.0f - s));
-    MCD_GATE_LANE(x) MCD_GATE_LANE(y) MCD_GATE_LANE(z) MCD_GATE_LANE(w)
-#undef MCD_GATE_LANE
-    dx1[i] = o1;
-    dx2[i] = o2;
-    dg[i] = og;
+    const float4 a = a4[i], b = b4[i], gg = g4[i];
+    float4 o;
+    o.x = gate_mix_one(a.x, b.x, gg.x);
+    o.y = gate_mix_one(a.y, b.y, gg.y);
+    o.z = gate_mix_one(a.z, b.z, gg.z);
+    o.w = gate_mix_one(a.w, b.w, gg.w);
+    o4[i] = o;
   }
+  for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    out[i] = gate_mix_one(x1[i], x2[i], g[i]);
+}
+
+__device__ __forceinline__ void gate_mix_bwd_one(float d, float a, float b, float g, float& o1, float& o2, float& og) {
+  const float s = gate_sigmoid(g);
+  o1 = d * s;
+  o2 = d * (1.0f - s);
+  og = d * (a - b) * (s * (1.0f - s));
+}
+
+__global__ __launch_bounds__(256) void gate_mix_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ x1,
+                                                           const float* __restrict__ x2, const float* __restrict__ g,
+                                                           float* __restrict__ dx1, float* __restrict__ dx2,
+                                                           float* __restrict__ dg, int64_t n4, int64_t n) {
+  const float4* d4 = reinterpret_cast<const float4*>(dy);
+  const float4* a4 = reinterpret_cast<const float4*>(x1);
+  const float4* b4 = reinterpret_cast<const float4*>(x2);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  float4* o14 = reinterpret_cast<float4*>(dx1);
+  float4* o24 = reinterpret_cast<float4*>(dx2);
+  float4* og4 = reinterpret_cast<float4*>(dg);
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
+    const float4 d = d4[i], a = a4[i], b = b4[i], gg = g4[i];
+    float4 o1, o2, og;
+    gate_mix_bwd_one(d.x, a.x, b.x, gg.x, o1.x, o2.x, og.x);
+    gate_mix_bwd_one(d.y, a.y, b.y, gg.y, o1.y, o2.y, og.y);
+    gate_mix_bwd_one(d.z, a.z, b.z, gg.z, o1.z, o2.z, og.z);
+    gate_mix_bwd_one(d.w, a.w, b.w, gg.w, o1.w, o2.w, og.w);
+    o14[i] = o1;
+    o24[i] = o2;
+    og4[i] = og;
+  }
+  for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    gate_mix_bwd_one(dy[i], x1[i], x2[i], g[i], dx1[i], dx2[i], dg[i]);
 }
 
 // one lane = one pixel, channels walked with stride HW (every per-channel access of a wave is a contiguous 256-B run)
@@ -168,9 +196,12 @@ int stream_blocks(int64_t n) {
 
 extern "C" int mcdseg_gate_mix_fwd(const float* x1, const float* x2, const float* g, float* out, int64_t n, void* stream) {
   MCD_REQUIRE(x1 && x2 && g && out, "gate_mix_fwd: null pointer");
-  MCD_REQUIRE(n > 0 && (n & 3) == 0, "gate_mix_fwd: element count must be a positive multiple of 4 (got %lld)", (long long)n);
-  hipLaunchKernelGGL(gate_mix_fwd_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float4*)x1,
-                     (const float4*)x2, (const float4*)g, (float4*)out, n / 4);
+  MCD_REQUIRE(n > 0, "gate_mix_fwd: element count must be positive (got %lld)", (long long)n);
+  const bool al = ((reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(x2) | reinterpret_cast<uintptr_t>(g) |
+                    reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const int64_t n4 = al ? n / 4 : 0;
+  hipLaunchKernelGGL(gate_mix_fwd_kernel, dim3(stream_blocks(n4 > 0 ? n4 : n)), dim3(256), 0, (hipStream_t)stream, x1, x2, g, out,
+                     n4, n);
   MCD_LAUNCH_CHECK("gate_mix_fwd");
   return 0;
 }
@@ -178,9 +209,13 @@ extern "C" int mcdseg_gate_mix_fwd(const float* x1, const float* x2, const float
 extern "C" int mcdseg_gate_mix_bwd(const float* dy, const float* x1, const float* x2, const float* g, float* dx1, float* dx2,
                                    float* dg, int64_t n, void* stream) {
   MCD_REQUIRE(dy && x1 && x2 && g && dx1 && dx2 && dg, "gate_mix_bwd: null pointer");
-  MCD_REQUIRE(n > 0 && (n & 3) == 0, "gate_mix_bwd: element count must be a positive multiple of 4 (got %lld)", (long long)n);
-  hipLaunchKernelGGL(gate_mix_bwd_kernel, dim3(stream_blocks(n / 4)), dim3(256), 0, (hipStream_t)stream, (const float4*)dy,
-                     (const float4*)x1, (const float4*)x2, (const float4*)g, (float4*)dx1, (float4*)dx2, (float4*)dg, n / 4);
+  MCD_REQUIRE(n > 0, "gate_mix_bwd: element count must be positive (got %lld)", (long long)n);
+  const bool al = ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(x1) | reinterpret_cast<uintptr_t>(x2) |
+                    reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(dx1) | reinterpret_cast<uintptr_t>(dx2) |
+                    reinterpret_cast<uintptr_t>(dg)) & 15) == 0;
+  const int64_t n4 = al ? n / 4 : 0;
+  hipLaunchKernelGGL(gate_mix_bwd_kernel, dim3(stream_blocks(n4 > 0 ? n4 : n)), dim3(256), 0, (hipStream_t)stream, dy, x1, x2, g,
+                     dx1, dx2, dg, n4, n);
   MCD_LAUNCH_CHECK("gate_mix_bwd");
   return 0;
 }

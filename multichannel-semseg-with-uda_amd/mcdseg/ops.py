@@ -1976,8 +1976,8 @@ class _GateMix(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x1, x2, g):
         x1, x2, g = _req(x1, "x1"), _req(x2, "x2"), _req(g, "gate logits")
-        if not (x1.shape == x2.shape == g.shape) or x1.numel() % 4:
-            raise ValueError("mcdseg: gate_mix needs three tensors of one shape with a multiple of 4 elements")
+        if not (x1.shape == x2.shape == g.shape):
+            raise ValueError("mcdseg: gate_mix needs three tensors of one shape")
         out = torch.empty_like(x1)
         check(lib().mcdseg_gate_mix_fwd(_p(x1), _p(x2), _p(g), _p(out), x1.numel(), _stream()), "gate_mix_fwd")
         ctx.save_for_backward(x1, x2, g)

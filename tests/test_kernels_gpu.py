@@ -461,7 +461,9 @@ def test_sgd_kernel_and_flat_optimizer():
     assert all(p.data_ptr() >= fp.data_ptr() and p.data_ptr() < fp.data_ptr() + 4 * fp.numel() for p in our_params)
 
 
-@pytest.mark.parametrize("shape", [(2, 41, 8, 12), (1, 3, 5, 7), (2, 3, 1, 9)])
+@pytest.mark.parametrize("shape", [(2, 41, 8, 12), (1, 3, 5, 7), (2, 3, 1, 9),
+                                   (1, 2, 1, 1), (1, 1, 3, 1), (2, 1, 1, 2),  # one column / one pixel: every tap clamps onto the same element
+                                   (1, 1, 129, 128)])                         # 16512 pixels: both grids are capped and their loops run twice
 def test_bilinear8_fwd_bwd(shape):
     dev = _dev()
     from mcdseg import ops
@@ -492,6 +494,46 @@ def test_mse(n):
     (3.0 * loss).backward()
     assert abs(float(loss) - float(ref)) <= 2e-6 * float(ref)
     _assert_close(pd.grad, gp, 2e-6, "mse grad")
+
+
+def _off_by_one_float(t, dev):
+    """the values of 1-D ``t`` on the GPU as ``base[1:1+n]``: contiguous, 4 bytes past a 16-byte boundary (mse's scalar form)"""
+    base = torch.zeros(t.numel() + 8, dtype=t.dtype, device=dev)
+    v = base[1:1 + t.numel()]
+    v.copy_(t)
+    assert v.is_contiguous() and v.data_ptr() % 16 == 4
+    return v
+
+
+@pytest.mark.parametrize("n", [1, 3, 5, 1001, 4099])
+def test_mse_tail_scalar_form_and_loss_only(n):
+    """mse at sizes below one float4, with a scalar tail and over two blocks (4099); for the last two sizes also with pred
+    and/or target 4 bytes off the 16-byte grid (the all-scalar form), each with and without a gradient buffer.  Bounds: test_mse's."""
+    dev = _dev()
+    from mcdseg import ops
+    g = torch.Generator().manual_seed(n)
+    p, t = torch.randn(n, generator=g), torch.randn(n, generator=g)
+    p64 = p.double().requires_grad_()
+    ref = F.mse_loss(p64, t.double())
+    (gp,) = torch.autograd.grad(3.0 * ref, p64)
+    places = [(False, False)] + ([(True, False), (False, True), (True, True)] if n >= 1001 else [])
+    for p_off, t_off in places:
+        pd = (_off_by_one_float(p, dev) if p_off else p.to(dev)).detach()
+        td = _off_by_one_float(t, dev) if t_off else t.to(dev)
+        assert pd.data_ptr() % 16 == (4 if p_off else 0) and td.data_ptr() % 16 == (4 if t_off else 0)
+        loss_only = ops.mse_loss(pd, td)
+        assert not loss_only.requires_grad
+        assert abs(float(loss_only) - float(ref)) <= 2e-6 * float(ref), (n, p_off, t_off)
+        pd.requires_grad_()
+        loss = ops.mse_loss(pd, td)
+        (3.0 * loss).backward()
+        assert abs(float(loss) - float(ref)) <= 2e-6 * float(ref), (n, p_off, t_off)
+        assert torch.equal(loss.detach(), loss_only)  # the gradient store does not touch the sum
+        _assert_close(pd.grad, gp, 2e-6, "mse grad n=%d offsets %s" % (n, (p_off, t_off)))
+    same = p.to(dev).requires_grad_()
+    zero = ops.mse_loss(same, p.to(dev))
+    zero.backward()
+    assert float(zero) == 0.0 and torch.equal(same.grad, torch.zeros(n, device=dev))
 
 
 def test_conv_bias_bn_relu():
