@@ -424,6 +424,45 @@ int mcdseg_prob_nll(const float* p, const int64_t* labels, const float* weight, 
                     float* grad, float* loss, int32_t N, int32_t C, int32_t HW, void* workspace, size_t workspace_bytes,
                     void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Boundary branch of the segmentation + boundary multitask decoder (MCDSegBDMultiTaskDecoder, models/dilated_fcn.py:1027-1222).
+ * H, W are the FULL resolution; every sum below leaves its block as an fp64 partial and is finished by one small kernel in fp64
+ * (no float atomics: results are bitwise reproducible); nothing synchronises with the host.
+ *   label_boundary (get_boundary, models/dilated_fcn.py:770-774): boundary[n,y,x] = 1 iff the max and the min of labels over the
+ *     3x3 neighbourhood differ, neighbours outside the image ignored (max_pool2d(x, 3, 1, 1) != -max_pool2d(-x, 3, 1, 1)).  labels:
+ *     int64 [N,H,W], or uint8 when labels_u8 != 0 (what mcdseg_predict_labels writes); every integer is just a value (no ignore
+ *     index).  Any H, W; eight pixels per thread in 16-byte label loads when W % 8 == 0 and labels is 16-byte aligned.
+ *   boundary_head (boundary_forward, :1118-1128, with upsample1-3 of :1050-1052): s1 [N,1,H/2,W/2], s2 [N,1,H/4,W/4],
+ *     s3 [N,1,H/8,W/8] -> p [N,1,H,W] = (sigmoid(up2 s1) + sigmoid(up4 s2) + sigmoid(up8 s3)) / 3, bilinear, align_corners = False.
+ *     H % 8 == 0, W % 8 == 0.  _bwd: dp -> ds1, ds2, ds3 in gather form (one thread per low-resolution pixel; sigmoid' is
+ *     recomputed from the s maps, nothing is kept from the forward pass).
+ *   bce2d (loss.py:131-138): beta = 1 - mean(t), w = 1 - beta + (2 beta - 1) t, loss = mean(w * bce(p, t)) in ONE pass over p and t:
+ *     sum(w bce) = (1 - beta) sum(bce) + (2 beta - 1) sum(t bce), so beta needs no pass of its own.  out[0] = loss, out[1] = beta.
+ *     target: uint8 {0,1} when target_u8 != 0, else fp32 (soft targets).  _bwd: dp = upstream/n * (p - t) / max(p (1 - p), 1e-12) * w in
+ *     one pass; beta is out[1] of the forward call and upstream a device scalar (NULL: 1), both read on the device.  The target gets
+ *     no gradient.  Edge arithmetic is that of today's F.binary_cross_entropy: bce = (t - 1) max(log1p(-p), -100) - t max(log p, -100)
+ *     (so p exactly 0 or 1 is a legal input and costs 100 per wrong pixel), NOT the reference era's log(p + 1e-12) / log(1 - p + 1e-12):
+ *     the two differ only for p within 1e-12 of 0 or 1, where the old form is bounded by 27.6 instead of 100.
+ *   boundary_head_bce (get_boundary_loss(pred_type="boundary"), :743-787 via :1202-1204): the train path fused -- out as for bce2d with
+ *     p = boundary_head(s1, s2, s3) and t = label_boundary(labels) (int64 labels, 16-byte aligned), neither stored; _bwd: one gather pass
+ *     per scale straight to ds1, ds2, ds3, p and t recomputed at the contributing pixels.  Equal to the composition of the three entry
+ *     points above: the gradients bit for bit, the loss up to the order of its partial sums.
+ * workspace: mcdseg_bce2d_workspace_bytes(N*H*W) bytes, 8-byte aligned, for bce2d and boundary_head_bce_fwd alike.
+ * ---------------------------------------------------------------------------------------------- */
+int mcdseg_label_boundary(const void* labels, int32_t labels_u8, uint8_t* boundary, int32_t N, int32_t H, int32_t W, void* stream);
+int mcdseg_boundary_head_fwd(const float* s1, const float* s2, const float* s3, float* p, int32_t N, int32_t H, int32_t W, void* stream);
+int mcdseg_boundary_head_bwd(const float* s1, const float* s2, const float* s3, const float* dp, float* ds1, float* ds2, float* ds3,
+                             int32_t N, int32_t H, int32_t W, void* stream);
+size_t mcdseg_bce2d_workspace_bytes(int64_t n);
+int mcdseg_bce2d(const float* p, const void* target, int32_t target_u8, float* out, int64_t n, void* workspace, size_t workspace_bytes,
+                 void* stream);
+int mcdseg_bce2d_bwd(const float* p, const void* target, int32_t target_u8, const float* beta, const float* upstream, float* dp, int64_t n,
+                     void* stream);
+int mcdseg_boundary_head_bce_fwd(const float* s1, const float* s2, const float* s3, const int64_t* labels, float* out, int32_t N, int32_t H,
+                                 int32_t W, void* workspace, size_t workspace_bytes, void* stream);
+int mcdseg_boundary_head_bce_bwd(const float* s1, const float* s2, const float* s3, const int64_t* labels, const float* beta,
+                                 const float* upstream, float* ds1, float* ds2, float* ds3, int32_t N, int32_t H, int32_t W, void* stream);
+
 /* Scale(img_shape, Image.BILINEAR) / Scale(img_shape, Image.NEAREST) in front of the two transforms below (transform.py:303,
  * 320; torchvision's Scale = PIL.Image.resize) on uint8 batches: src [N,H,W,C] -> dst [N,OH,OW,C] (bilinear; Pillow's 8-bit
  * ImagingResample, bit for bit) and src [N,H,W] -> dst [N,OH,OW] (nearest; ImagingScaleAffine, for label maps).  workspace: 4-byte

@@ -4,6 +4,7 @@
   ProbCrossEntropyLoss2d       loss.py:16-30   weighted NLL of log(p) for probability maps (gated MFNet fusions)
   Diff2d                       loss.py:93-100  mean |softmax(o1) - softmax(o2)|
   get_prob_distance_criterion  loss.py:192-210 ("diff" is the default ``--d_loss``, argmyparse.py:131)
+  bce2d                        loss.py:131-138 class-balanced binary cross-entropy (the seg + boundary multitask decoder)
 
 All criteria are thin ``nn.Module`` shells over ``mcdseg.ops`` (forward value and d/dlogits come out of
 one streaming pass).  ``DiscrepancyLoss`` is an alias of ``Diff2d`` (BASELINE.json uses that name; the
@@ -157,6 +158,25 @@ class MisSymKLD(nn.Module):
 
 
 SpatialJSD2d = MisSymKLD
+
+
+def bce2d(input, target):
+    """loss.py:131-138: beta = 1 - mean(target), weights = 1 - beta + (2 beta - 1) target, the weighted mean binary cross-entropy.
+    The reference hands F.binary_cross_entropy an [N,1,H,W] input with an [N,H,W] target, which the torch of its day took for
+    equal element counts; both are flattened here.  fp32 GPU tensors (target fp32, or uint8 as ``ops.label_boundary`` writes
+    it) run ``ops.bce2d`` -- one HIP pass forward, one backward; anything else evaluates the torch expression below, which is also
+    the statement of what the kernel computes (logs clamped at -100 as today's F.binary_cross_entropy does, where the reference
+    era added 1e-12 inside the log)."""
+    assert not target.requires_grad, \
+        "nn criterions don't compute the gradient w.r.t. targets - please mark these variables as not requiring gradients"
+    if input.numel() != target.numel():
+        raise ValueError("bce2d: input %s and target %s differ in size" % (tuple(input.shape), tuple(target.shape)))
+    if input.is_cuda and target.is_cuda and input.dtype == torch.float32 and target.dtype in (torch.float32, torch.uint8):
+        return ops.bce2d(input, target)
+    target = target.reshape(input.shape).to(input.dtype)
+    beta = 1 - torch.mean(target)
+    weights = 1 - beta + (2 * beta - 1) * target
+    return F.binary_cross_entropy(input, target, weights, reduction="mean")
 
 
 def get_prob_distance_criterion(criterion_name, n_class=None):

@@ -1767,6 +1767,139 @@ def mse_loss(pred, target):
     return _MSE.apply(pred, target)
 
 
+# ------------------------------------------------------------------------------------------------ boundary branch (seg + boundary decoder)
+def _ws64(nbytes, device):
+    return torch.empty(int(nbytes) // 8 + 1, dtype=torch.float64, device=device)
+
+
+def _req_labels(t, name):
+    """an integer label map: int64, or the uint8 ``predict_labels`` writes"""
+    if t is not None and t.is_cuda and t.dtype not in (torch.int64, torch.uint8):
+        raise TypeError("mcdseg: %s must be torch.int64 or torch.uint8, got %s" % (name, t.dtype))
+    return _req(t, name, t.dtype if t is not None and t.is_cuda else torch.int64)
+
+
+def label_boundary(labels):
+    """uint8 [N,H,W]: 1 where the 3x3 dilation and the 3x3 erosion of the label map differ (``get_boundary``,
+    models/dilated_fcn.py:770-774); labels int64 or uint8 [N,H,W]"""
+    labels = _req_labels(labels, "labels")
+    if labels.dim() != 3:
+        raise ValueError("mcdseg: label_boundary takes labels [N,H,W], got %s" % (tuple(labels.shape),))
+    n, h, w = labels.shape
+    out = torch.empty((n, h, w), dtype=torch.uint8, device=labels.device)
+    check(lib().mcdseg_label_boundary(_p(labels), int(labels.dtype == torch.uint8), _p(out), n, h, w, _stream()), "label_boundary")
+    return out
+
+
+def _head_maps(s1, s2, s3):
+    s1, s2, s3 = _req(s1, "boundary map s1"), _req(s2, "boundary map s2"), _req(s3, "boundary map s3")
+    if s3.dim() != 4 or s3.shape[1] != 1:
+        raise ValueError("mcdseg: the boundary head takes 1-channel maps [N,1,h,w], got %s" % (tuple(s3.shape),))
+    n, _, h8, w8 = s3.shape
+    if tuple(s1.shape) != (n, 1, 4 * h8, 4 * w8) or tuple(s2.shape) != (n, 1, 2 * h8, 2 * w8):
+        raise ValueError("mcdseg: the boundary head takes maps at 1/2, 1/4 and 1/8 of one resolution, got %s, %s, %s"
+                         % (tuple(s1.shape), tuple(s2.shape), tuple(s3.shape)))
+    return s1, s2, s3, n, 8 * h8, 8 * w8
+
+
+class _BoundaryHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s1, s2, s3):
+        s1, s2, s3, n, h, w = _head_maps(s1, s2, s3)
+        p = torch.empty((n, 1, h, w), dtype=torch.float32, device=s1.device)
+        check(lib().mcdseg_boundary_head_fwd(_p(s1), _p(s2), _p(s3), _p(p), n, h, w, _stream()), "boundary_head_fwd")
+        ctx.save_for_backward(s1, s2, s3)
+        return p
+
+    @staticmethod
+    def backward(ctx, dp):
+        s1, s2, s3 = ctx.saved_tensors
+        dp = _req(dp, "grad_output")
+        n, _, h, w = dp.shape
+        d1, d2, d3 = torch.empty_like(s1), torch.empty_like(s2), torch.empty_like(s3)
+        check(lib().mcdseg_boundary_head_bwd(_p(s1), _p(s2), _p(s3), _p(dp), _p(d1), _p(d2), _p(d3), n, h, w, _stream()), "boundary_head_bwd")
+        return d1, d2, d3
+
+
+def boundary_head(s1, s2, s3):
+    """(sigmoid(up2 s1) + sigmoid(up4 s2) + sigmoid(up8 s3)) / 3, bilinear with align_corners=False
+    (MCDSegBDMultiTaskDecoder.boundary_forward behind its three 1x1 projections, models/dilated_fcn.py:1118-1128)"""
+    return _BoundaryHead.apply(s1, s2, s3)
+
+
+def _bce_target(t):
+    if t is not None and t.is_cuda and t.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("mcdseg: bce2d target must be torch.uint8 or torch.float32, got %s" % (t.dtype,))
+    return _req(t, "bce2d target", t.dtype if t is not None and t.is_cuda else torch.float32)
+
+
+class _BCE2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, target):
+        L = lib()
+        p, target = _req(p, "bce2d input"), _bce_target(target)
+        if p.numel() != target.numel():
+            raise ValueError("mcdseg: bce2d shapes differ: %s vs %s" % (tuple(p.shape), tuple(target.shape)))
+        n = p.numel()
+        out = torch.empty(2, dtype=torch.float32, device=p.device)
+        ws = _ws64(L.mcdseg_bce2d_workspace_bytes(n), p.device)
+        check(L.mcdseg_bce2d(_p(p), _p(target), int(target.dtype == torch.uint8), _p(out), n, _p(ws), ctypes.c_size_t(ws.numel() * 8),
+                             _stream()), "bce2d")
+        ctx.save_for_backward(p, target, out)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, grad_out, _):
+        p, target, out = ctx.saved_tensors
+        g = _req(grad_out.reshape(1), "grad_output")
+        dp = torch.empty_like(p)
+        check(lib().mcdseg_bce2d_bwd(_p(p), _p(target), int(target.dtype == torch.uint8), _p(out[1:]), _p(g), _p(dp), p.numel(), _stream()),
+              "bce2d_bwd")
+        return dp, None
+
+
+def bce2d(p, target, return_beta=False):
+    """class-balanced binary cross-entropy (loss.py:131-138): beta = 1 - mean(t), mean((1 - beta + (2 beta - 1) t) * bce(p, t)) in one
+    pass; gradient to ``p`` only.  target: uint8 {0,1} or fp32, as many elements as p."""
+    if target.requires_grad:
+        raise ValueError("mcdseg: bce2d does not compute the gradient w.r.t. its target")
+    loss, out = _BCE2d.apply(p, target)
+    return (loss, out[1]) if return_beta else loss
+
+
+class _BoundaryHeadBCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s1, s2, s3, labels):
+        L = lib()
+        s1, s2, s3, n, h, w = _head_maps(s1, s2, s3)
+        labels = _req(labels, "labels", torch.int64)
+        if tuple(labels.shape) != (n, h, w):
+            raise ValueError("mcdseg: labels %s do not match the boundary maps' resolution %s" % (tuple(labels.shape), (n, h, w)))
+        out = torch.empty(2, dtype=torch.float32, device=s1.device)
+        ws = _ws64(L.mcdseg_bce2d_workspace_bytes(n * h * w), s1.device)
+        check(L.mcdseg_boundary_head_bce_fwd(_p(s1), _p(s2), _p(s3), _p(labels), _p(out), n, h, w, _p(ws), ctypes.c_size_t(ws.numel() * 8),
+                                             _stream()), "boundary_head_bce_fwd")
+        ctx.save_for_backward(s1, s2, s3, labels, out)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        s1, s2, s3, labels, out = ctx.saved_tensors
+        g = _req(grad_out.reshape(1), "grad_output")
+        n, h, w = labels.shape
+        d1, d2, d3 = torch.empty_like(s1), torch.empty_like(s2), torch.empty_like(s3)
+        check(lib().mcdseg_boundary_head_bce_bwd(_p(s1), _p(s2), _p(s3), _p(labels), _p(out[1:]), _p(g), _p(d1), _p(d2), _p(d3), n, h, w,
+                                                 _stream()), "boundary_head_bce_bwd")
+        return d1, d2, d3, None
+
+
+def boundary_head_bce(s1, s2, s3, labels):
+    """``bce2d(boundary_head(s1, s2, s3), label_boundary(labels))`` without the two full-resolution maps, forward and backward
+    (get_boundary_loss(pred_type="boundary"), models/dilated_fcn.py:743-787, 1202-1204); labels int64 [N,H,W]"""
+    return _BoundaryHeadBCE.apply(s1, s2, s3, labels)
+
+
 # ------------------------------------------------------------------------------------------------ losses
 def label_weight_sum(labels, class_weight, n_class, ignore_index=-100):
     """device scalar sum_i w[labels_i]"""

@@ -5,6 +5,9 @@
   DRNSegPixelClassifier     = F1/F2   :340-366  learned x8 depthwise transposed-conv up-sampler
   FusionDRNSegPixelClassifier         :431-470  fuse features, one up-sampler
   ScoreFusionDRNSegPixelClassifier    :473-491  one up-sampler per modality, fuse scores
+  MultiTaskEncoder / MCDMultiTaskDecoder            :554-566, 661-739   segmentation + HHA regression (cfg4)
+  MultiTaskEncoderReturningMultipleFeaturemaps / get_boundary_loss / MCDSegBDMultiTaskDecoder
+                                      :569-629, 743-787, 1027-1222      segmentation + boundary ("segbd")
 
 State-dict keys follow the reference: ``base.<stage>...``, ``seg.{weight,bias}``,
 ``up.weight`` / ``up1.weight`` / ``up2.weight``.
@@ -18,7 +21,7 @@ from torch.nn import Parameter
 from mcdseg import ops
 
 from . import drn
-from .drn import BatchNorm2d, Conv2d, FusedSequential, run_fused
+from .drn import BatchNorm2d, Conv2d, FusedSequential, _has_hooks, run_fused
 from .fusion import AddFusion, ConcatFusion, get_fusion_model
 
 
@@ -261,3 +264,161 @@ class MCDMultiTaskDecoder(nn.Module):
     def get_task_weights(self):
         import numpy as np
         return (np.sqrt(np.exp(2 * self.s_semsegcls.data.cpu().numpy())), np.sqrt(np.exp(2 * self.s_deprgr.data.cpu().numpy())))
+
+
+# ------------------------------------------------------------------------------------------------ segmentation + boundary ("segbd")
+class MultiTaskEncoderReturningMultipleFeaturemaps(nn.Module):
+    """The DRN stages as ``main_layer0`` .. ``main_layer8``, returning every stage's output ``h0`` .. ``h8``
+    (models/dilated_fcn.py:569-629).  The stages run as on the trunk's stage-tap path (``DRN._forward`` with ``out_middle``): each
+    one writes an ordinary fp32 output, so the decoder's gradients into ``h2``, ``h3`` and ``h8`` meet the main path's in autograd.
+    Compact activation storage keeps no fp32 stage outputs and is refused."""
+
+    def __init__(self, model_name, pretrained=True, input_ch=3):
+        super().__init__()
+        ctor = drn.__dict__.get(model_name)
+        if ctor is None or not model_name.startswith("drn_"):
+            raise NotImplementedError("unknown DRN variant %r" % (model_name,))
+        model = ctor(pretrained=pretrained, num_classes=0, input_ch=input_ch)
+        if "drn_d" in model_name:
+            self.main_layer0 = model.layer0
+        else:
+            self.main_layer0 = FusedSequential(model.conv1, model.bn1, model.relu)
+        for k in range(1, 9):
+            stage = getattr(model, "layer%d" % k)
+            if stage is None:
+                raise NotImplementedError("%s has no layer%d: the multi-feature-map encoder needs all nine stages" % (model_name, k))
+            setattr(self, "main_layer%d" % k, stage)
+
+    def forward(self, x):
+        if ops.ACT_STORAGE == "compact":
+            raise NotImplementedError("MultiTaskEncoderReturningMultipleFeaturemaps hands out the fp32 outputs of its stages: it does not "
+                                      "run with MCDSEG_ACT_STORAGE=compact (nor the 2-byte chain built on it); use fp32 storage")
+        out = {}
+        with ops.late_weight_grads(self):
+            for k in range(9):
+                stage = getattr(self, "main_layer%d" % k)
+                if type(stage) is FusedSequential and not _has_hooks(stage):
+                    x = run_fused(list(stage.children()), x)
+                else:
+                    x = stage(x)
+                out["h%d" % k] = x
+        return out
+
+
+def _get_boundary(var):
+    """``get_boundary`` of models/dilated_fcn.py:770-774: 3x3 dilation != 3x3 erosion"""
+    if var.is_cuda and var.dim() == 3 and var.dtype in (torch.int64, torch.uint8):
+        return ops.label_boundary(var)
+    v = var.float()
+    v4 = v if v.dim() == 4 else v[:, None]
+    dilation = nn.functional.max_pool2d(v4, kernel_size=3, stride=1, padding=1)
+    erosion = -nn.functional.max_pool2d(-v4, kernel_size=3, stride=1, padding=1)
+    return (dilation != erosion).reshape(v.shape)
+
+
+def get_boundary_loss(pred, gt, pred_type="semseg", gt_type="semseg"):
+    """models/dilated_fcn.py:743-787: class-balanced BCE between a boundary prediction and a boundary target, either of which may be
+    given as a label map ("semseg": its boundary is taken) or as a boundary map ("boundary"; a target is detached)."""
+    from loss import bce2d
+    assert pred_type in ["semseg", "boundary"]
+    assert gt_type in ["semseg", "boundary"]
+    gt_boundary = _get_boundary(gt) if gt_type == "semseg" else gt.detach()
+    pred_boundary = _get_boundary(pred) if pred_type == "semseg" else pred
+    if gt_boundary.dtype != torch.uint8 or not gt_boundary.is_cuda:
+        gt_boundary = gt_boundary.to(pred_boundary.dtype if pred_boundary.dtype.is_floating_point else torch.float32)
+    return bce2d(pred_boundary.float(), gt_boundary)
+
+
+class MCDSegBDMultiTaskDecoder(nn.Module):
+    """Two segmentation heads on ``h8`` + a HED-style boundary head on ``h2``, ``h3``, ``h8`` (three 1-channel 1x1 projections,
+    bilinear x2 / x4 / x8, mean of the three sigmoids), learned log-variance task weights (models/dilated_fcn.py:1027-1222).
+    ``semseg_shortcut`` (full-resolution 512-channel decoders) and ``use_seg2bd_conv`` (a 5x5 convolution on the logits) are not
+    built; ``depth_shortcut`` is accepted and ignored, as in the reference."""
+
+    def __init__(self, n_class, depth_ch, semseg_criterion=None, discrepancy_criterion=None, semseg_shortcut=False,
+                 depth_shortcut=False, add_pred_seg_boundary_loss=False, use_seg2bd_conv=False):
+        super().__init__()
+        if semseg_shortcut:
+            raise NotImplementedError("semseg_shortcut (segmentation decoders on full-resolution 512-channel maps) is not implemented")
+        if use_seg2bd_conv:
+            raise NotImplementedError("use_seg2bd_conv (a 5x5 boundary convolution on the segmentation logits) is not implemented")
+        self.s_semsegcls = Parameter(torch.ones(1))
+        self.s_boundary = Parameter(torch.ones(1))
+        self.semsegcls_dec1 = ThreeLayerDecoder(n_class)
+        self.semsegcls_dec2 = ThreeLayerDecoder(n_class)
+        self.semseg_criterion = semseg_criterion
+        self.discrepancy_criterion = discrepancy_criterion
+        self.upsample3 = _Bilinear8()
+        self.conv1 = Conv2d(32, 1, kernel_size=1, stride=1, padding=0)
+        self.conv2 = Conv2d(64, 1, kernel_size=1, stride=1, padding=0)
+        self.conv3 = Conv2d(512, 1, kernel_size=1, stride=1, padding=0)
+        self.semseg_shortcut = semseg_shortcut
+        self.depth_shortcut = depth_shortcut
+        self.add_pred_seg_boundary_loss = add_pred_seg_boundary_loss
+        self.use_seg2bd_conv = use_seg2bd_conv
+        if self.add_pred_seg_boundary_loss:
+            self.s_pred_seg_boundary = Parameter(torch.ones(1))
+
+    def semseg_forward(self, x_dic):
+        return self.upsample3(self.semsegcls_dec1(x_dic["h8"])), self.upsample3(self.semsegcls_dec2(x_dic["h8"]))
+
+    def _boundary_maps(self, x_dic):
+        return self.conv1(x_dic["h2"]), self.conv2(x_dic["h3"]), self.conv3(x_dic["h8"])
+
+    def boundary_forward(self, x_dic):
+        return ops.boundary_head(*self._boundary_maps(x_dic))
+
+    def forward(self, x_dic):
+        pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic)
+        return pred_semseg1, pred_semseg2, self.boundary_forward(x_dic)
+
+    def get_cls_descrepancy(self, x_dic):
+        pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic)
+        return self.discrepancy_criterion(pred_semseg1, pred_semseg2)
+
+    @staticmethod
+    def _argmax_labels(pred_semseg):
+        """``pred.max(1)[1]`` as a label map (gradient-free): uint8 from the predict kernel on the GPU"""
+        pred = pred_semseg.detach()
+        if pred.is_cuda and pred.dtype == torch.float32 and pred.shape[1] <= 255:
+            return ops.predict_labels(pred)[0]
+        return pred.max(1)[1]
+
+    def get_semseg_loss(self, x_dic, gt_semseg, separately_returning=False):
+        pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic)
+        loss1 = self.semseg_criterion(pred_semseg1, gt_semseg)
+        loss2 = self.semseg_criterion(pred_semseg2, gt_semseg)
+        # the "extra" losses (:1145-1153): the arg-max boundary of each head against the labels' -- values without a gradient
+        loss1 = loss1 + get_boundary_loss(self._argmax_labels(pred_semseg1), gt_semseg)
+        loss2 = loss2 + get_boundary_loss(self._argmax_labels(pred_semseg2), gt_semseg)
+        return (loss1, loss2) if separately_returning else loss1 + loss2
+
+    def get_psuedo_boundary_loss(self, x_dic, separately_returning=False):
+        """:1183-1200.  The prediction is an arg-max and the target is detached, so the reference's value carries no gradient either:
+        it is computed without a tape."""
+        assert self.add_pred_seg_boundary_loss
+        with torch.no_grad():
+            psuedo_boundary = self.boundary_forward(x_dic)
+            pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic)
+            loss1 = get_boundary_loss(pred=self._argmax_labels(pred_semseg1), gt=psuedo_boundary, gt_type="boundary")
+            loss2 = get_boundary_loss(pred=self._argmax_labels(pred_semseg2), gt=psuedo_boundary, gt_type="boundary")
+        return (loss1, loss2) if separately_returning else loss1 + loss2
+
+    def get_boundary_loss(self, x_dic, gt_semseg):
+        s1, s2, s3 = self._boundary_maps(x_dic)
+        if s1.is_cuda and gt_semseg.is_cuda and gt_semseg.dtype == torch.int64:
+            return ops.boundary_head_bce(s1, s2, s3, gt_semseg)  # the head, the target and the loss in one pass each way
+        return get_boundary_loss(pred=ops.boundary_head(s1, s2, s3), gt=gt_semseg, pred_type="boundary")
+
+    def get_loss(self, x, gt_semseg, separately_returning=False):
+        loss1, loss2 = self.get_semseg_loss(x, gt_semseg, separately_returning=True)
+        s = self.s_semsegcls
+        semseg_loss = ((torch.exp(-s) * loss1 + s) + (torch.exp(-s) * loss2 + s)) / 2
+        boundary_loss = torch.exp(-self.s_boundary) * self.get_boundary_loss(x, gt_semseg) + self.s_boundary
+        return (semseg_loss, boundary_loss) if separately_returning else semseg_loss + boundary_loss
+
+    def get_task_weights(self):
+        """the reference reads ``self.s_deprgr`` here (:1221), which this decoder does not have -- the call raises there; the second
+        value is the boundary task's standard deviation"""
+        import numpy as np
+        return (np.sqrt(np.exp(2 * self.s_semsegcls.data.cpu().numpy())), np.sqrt(np.exp(2 * self.s_boundary.data.cpu().numpy())))

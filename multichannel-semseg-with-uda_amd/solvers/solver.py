@@ -358,3 +358,77 @@ class MultiTaskMCDSolver:
             loss.backward()
             self.opt_enc.step()
         return c_loss, loss.detach() / self.num_k, parts
+
+
+class SegBDMultiTaskMCDSolver:
+    """Three-step update of the segmentation + boundary multitask variant (two segmentation decoders and a boundary head on a
+    stage-tap RGB encoder), statement for statement after ``adapt_segbd_multitask_trainer.py:193-257``:
+
+      A  enc, dec <- min  semseg(src) + boundary(src) [+ scale_bd_loss * pseudo-boundary(tgt), once epoch > boundary_loss_converging_epoch]
+      B  dec      <- min  semseg(src) - discrepancy(tgt)
+      C  enc      <- min  discrepancy(tgt) * num_multiply_d_loss          (num_k times)
+
+    Elisions, each of which provably changes no result: the encoder runs without a tape where no gradient can reach it or where its
+    gradient is discarded before any use -- step A's target pass (the pseudo-boundary loss is gradient-free: an arg-max against a
+    detached target) and both passes of step B (only the decoder's optimizer steps there, and step C zeroes the encoder's gradients
+    first).  Every forward of the reference still runs, so the BatchNorm running statistics move as they do there.  Nothing else of
+    ``MultiTaskMCDSolver``'s machinery (the two-stream fork, the re-used target forward) is taken over: the plain sequence runs."""
+
+    def __init__(self, model_enc, model_dec, optimizer_enc, optimizer_dec, num_k=4, num_multiply_d_loss=1,
+                 add_pred_seg_boundary_loss=False, boundary_loss_converging_epoch=5, scale_bd_loss=1):
+        self.enc, self.dec = model_enc, model_dec
+        self.opt_enc, self.opt_dec = optimizer_enc, optimizer_dec
+        self.num_k, self.mult = num_k, num_multiply_d_loss
+        self.add_pred_seg_boundary_loss = add_pred_seg_boundary_loss
+        self.boundary_loss_converging_epoch = boundary_loss_converging_epoch
+        self.scale_bd_loss = scale_bd_loss
+
+    def step(self, src_imgs, src_gt_semseg, tgt_imgs, epoch=0):
+        """returns (c_loss, d_loss, (src_semseg_loss, src_boundary_loss, tgt_psuedo_boundary_loss)) -- step A's values, which are
+        the ones the trainer logs"""
+        enc, dec = self.enc, self.dec
+        src_rgbs, tgt_rgbs = src_imgs[:, :3, :, :], tgt_imgs[:, :3, :, :]
+
+        # ---- A: encoder and decoder on source (+ the target's pseudo boundary)
+        self.opt_enc.zero_grad()
+        self.opt_dec.zero_grad()
+        src_fet = enc(src_rgbs)
+        with torch.no_grad():
+            tgt_fet = enc(tgt_rgbs)
+        src_semseg_loss, src_boundary_loss = dec.get_loss(src_fet, src_gt_semseg, separately_returning=True)
+        tgt_psuedo_boundary_loss = 0
+        if epoch > self.boundary_loss_converging_epoch and self.add_pred_seg_boundary_loss:
+            tgt_psuedo_boundary_loss = dec.get_psuedo_boundary_loss(tgt_fet, separately_returning=False) * self.scale_bd_loss
+        del tgt_fet
+        loss = src_semseg_loss + src_boundary_loss + tgt_psuedo_boundary_loss
+        loss.backward()
+        c_loss = loss.detach()
+        parts = (src_semseg_loss.detach(), src_boundary_loss.detach(),
+                 tgt_psuedo_boundary_loss.detach() if torch.is_tensor(tgt_psuedo_boundary_loss) else tgt_psuedo_boundary_loss)
+        del src_fet
+        self.opt_enc.step()
+        self.opt_dec.step()
+
+        # ---- B: decoder only
+        self.opt_enc.zero_grad()
+        self.opt_dec.zero_grad()
+        with torch.no_grad():
+            src_fet = enc(src_rgbs)
+        src_semseg_loss, _ = dec.get_loss(src_fet, src_gt_semseg, separately_returning=True)
+        with torch.no_grad():
+            tgt_fet = enc(tgt_rgbs)
+        tgt_discrepancy = dec.get_cls_descrepancy(tgt_fet)
+        loss = src_semseg_loss - tgt_discrepancy
+        loss.backward()
+        del src_fet, tgt_fet
+        self.opt_dec.step()
+
+        # ---- C: encoder only, num_k times
+        for _ in range(self.num_k):
+            self.opt_enc.zero_grad()
+            tgt_fet = enc(tgt_rgbs)
+            loss = dec.get_cls_descrepancy(tgt_fet) * self.mult
+            loss.backward()
+            del tgt_fet
+            self.opt_enc.step()
+        return c_loss, loss.detach() / self.num_k, parts
