@@ -22,108 +22,60 @@ import numpy as np
 import torch
 from PIL import Image
 
+import tester_common
 from argmyparse import add_additional_params_to_args, get_da_mcd_testing_parser
-from datasets import get_dataset
-from eval import ConfusionMeter
-from loss import CrossEntropyLoss2d, get_prob_distance_criterion
 from models.model_util import get_segbd_multitask_models
-from util import check_if_done, get_class_weight_from_file, load_checkpoint, mkdir_if_not_exist, save_dic_to_json
+from trainer_common import criteria
+from util import mkdir_if_not_exist
 from mcdseg import ops
 
 
-def _unwrap(m):
-    return m.module if isinstance(m, torch.nn.DataParallel) else m
-
-
 def main(argv=None):
-    args = get_da_mcd_testing_parser().parse_args(argv)
-    args = add_additional_params_to_args(args)
-    if not torch.cuda.is_available():
-        raise SystemExit("this tester runs on an MI355X: the HIP kernels are the only implementation (no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    indir, infn = os.path.split(args.trained_checkpoint)
-    trained_mode = indir.split(os.path.sep)[-2]
-    args.mode = "%s---%s-%s" % (trained_mode, args.tgt_dataset, args.split)
-    model_name = infn.replace(".pth", "") + ("-use_f2" if args.use_f2 else "")
-    if not os.path.exists(args.trained_checkpoint):
-        raise OSError("%s does not exist!" % args.trained_checkpoint)
-    checkpoint = load_checkpoint(args.trained_checkpoint)
-    train_args = checkpoint["args"]
-    args.start_epoch = checkpoint["epoch"]
-    base_outdir = os.path.join(args.outdir, args.mode, model_name)
-    mkdir_if_not_exist(base_outdir)
-    json_fn = os.path.join(base_outdir, "param.json")
-    check_if_done(json_fn)
-    save_dic_to_json(dict(vars(args)), json_fn, verbose=False)
+    args = add_additional_params_to_args(get_da_mcd_testing_parser().parse_args(argv))
+    t = tester_common.start(args)
+    train_args = t.train_args
 
-    train_img_shape = [int(x) for x in train_args.train_img_shape]
-    test_img_shape = tuple(int(x) for x in args.test_img_shape)
-    spec = dict(length=args.synthetic_len, img_shape=train_img_shape, n_class=train_args.n_class, seed=args.seed) if args.synthetic else None
-    tgt_dataset = get_dataset(dataset_name=args.tgt_dataset, split=args.split, img_transform=None, label_transform=None, test=True,
-                              input_ch=train_args.input_ch, synthetic=spec)
-    loader = torch.utils.data.DataLoader(tgt_dataset, batch_size=args.batch_size, pin_memory=True)
-
-    os.environ["MCDSEG_PRETRAINED"] = "0"  # weights come from the checkpoint
     # the criteria are not used here, but the decoder holds the class weights as a buffer (semseg_criterion.nll_loss.weight) and the
     # checkpoint carries it, so they are built as the trainer built them (adapt_segbd_multitask_tester.py:76-93)
-    weight = get_class_weight_from_file(n_class=train_args.n_class, weight_filename=train_args.loss_weights_file,
-                                        add_bg_loss=train_args.add_bg_loss)
+    criterion, criterion_d = criteria(train_args)
     model_enc, model_dec = get_segbd_multitask_models(
         net_name=train_args.net, input_ch=train_args.input_ch, n_class=train_args.n_class,
-        is_data_parallel=getattr(train_args, "is_data_parallel", False), semseg_criterion=CrossEntropyLoss2d(weight),
-        discrepancy_criterion=get_prob_distance_criterion(train_args.d_loss, n_class=train_args.n_class),
+        is_data_parallel=getattr(train_args, "is_data_parallel", False), semseg_criterion=criterion, discrepancy_criterion=criterion_d,
         semseg_shortcut=getattr(train_args, "semseg_shortcut", False), depth_shortcut=getattr(train_args, "depth_shortcut", False),
         add_pred_seg_boundary_loss=getattr(train_args, "add_pred_seg_boundary_loss", False),
         use_seg2bd_conv=getattr(train_args, "use_seg2bd_conv", False))
-    model_enc.load_state_dict(checkpoint["enc_state_dict"])
-    model_dec.load_state_dict(checkpoint["dec_state_dict"])
-    enc, dec = _unwrap(model_enc), _unwrap(model_dec)
+    model_enc.load_state_dict(t.checkpoint["enc_state_dict"])
+    model_dec.load_state_dict(t.checkpoint["dec_state_dict"])
+    enc, dec = tester_common.unwrap(model_enc), tester_common.unwrap(model_dec)
     print(dec.get_task_weights())
     for m in (model_enc, model_dec):
         m.eval()
-        m.to(dev)
-    n_used = args.n_class if getattr(train_args, "add_bg_loss", False) else args.n_class - 1
+        m.to(t.dev)
 
-    label_outdir = os.path.join(base_outdir, "label")
-    boundary_outdir = os.path.join(base_outdir, "boundary")
+    label_outdir = os.path.join(t.base_outdir, "label")
+    boundary_outdir = os.path.join(t.base_outdir, "boundary")
     mkdir_if_not_exist(label_outdir)
     mkdir_if_not_exist(boundary_outdir)
     total_ent, images = 0.0, 0
-    meter = ConfusionMeter(train_args.n_class, background_id=255, device=dev)
     with torch.no_grad():
-        for imgs, gts, paths in loader:
-            imgs = imgs.to(dev, non_blocking=True)
+        for imgs, gts, paths in t.loader:
+            imgs = imgs.to(t.dev, non_blocking=True)
             feature = enc(imgs[:, :3, :, :].contiguous())
             s1 = dec.semsegcls_dec1(feature["h8"])  # pred_semseg1 before the x8 up-sampling
             pred_boundary = dec.boundary_forward(feature)
-            labels, ent = ops.predict_labels_bilinear8(s1, n_used)
+            labels, ent = ops.predict_labels_bilinear8(s1, t.n_used)
             total_ent += float(ent) * len(paths)  # the reference's mean over images (it runs one image per batch)
             images += len(paths)
-            if torch.is_tensor(gts) and gts.dim() == 3 and tuple(gts.shape) == tuple(labels.shape):
-                gts = gts.to(dev)
-                meter.update(labels, torch.where(gts == train_args.n_class - 1, torch.full_like(gts, 255), gts))
+            tester_common.update_meter(t.meter, labels, gts, train_args.n_class)
             if args.saves_prob:
-                prob_outdir = os.path.join(base_outdir, "prob")
-                mkdir_if_not_exist(prob_outdir)
-                full = ops.bilinear8(s1)
-                for k, path in enumerate(paths):
-                    np.save(os.path.join(prob_outdir, os.path.basename(path).replace("png", "npy")), full[k].cpu().numpy())
-                del full
-            lab = ops.resize_u8(labels, test_img_shape, nearest=True).cpu().numpy()
+                tester_common.save_probs(t.base_outdir, paths, ops.bilinear8(s1))
+            lab = ops.resize_u8(labels, t.test_img_shape, nearest=True).cpu().numpy()
             boundary = np.uint8(pred_boundary[:, 0].cpu().numpy() * 255)
             for k, path in enumerate(paths):
                 name = os.path.basename(path)
                 Image.fromarray(lab[k]).save(os.path.join(label_outdir, name))
-                Image.fromarray(boundary[k]).resize(test_img_shape, Image.BILINEAR).save(os.path.join(boundary_outdir, name))
-    ave_ent = total_ent / max(images, 1)
-    print("average entropy: %s" % ave_ent)
-    with open(os.path.join(base_outdir, "ave_ent_%s.txt" % ave_ent), "w") as f:
-        f.write(str(ave_ent))
-    if int(meter.hist.sum()) > 0:
-        summary = meter.summary()
-        save_dic_to_json(summary, os.path.join(base_outdir, "eval_result.json"), verbose=False)
-        print("pixAcc %.2f  mAcc %.2f  fwIoU %.2f  mIoU %.2f" % (summary["pixAcc"], summary["mAcc"], summary["fwIoU"], summary["mIoU"]))
-    return label_outdir, boundary_outdir, ave_ent
+                Image.fromarray(boundary[k]).resize(t.test_img_shape, Image.BILINEAR).save(os.path.join(boundary_outdir, name))
+    return label_outdir, boundary_outdir, tester_common.finish(t.base_outdir, total_ent, images, t.meter)
 
 
 if __name__ == "__main__":

@@ -21,11 +21,11 @@ import numpy as np
 import torch
 from PIL import Image
 
+import tester_common
 from argmyparse import add_additional_params_to_args
-from datasets import AVAILABLE_DATASET_LIST, get_dataset
-from eval import ConfusionMeter
+from datasets import AVAILABLE_DATASET_LIST
 from models.model_util import get_full_model
-from util import check_if_done, load_checkpoint, mkdir_if_not_exist, save_dic_to_json
+from util import mkdir_if_not_exist
 from mcdseg import ops
 
 
@@ -55,14 +55,9 @@ def add_subdir_if_necessary(outdir, subdir, tgt_dataset):
 
 
 def main(argv=None):
-    args = get_parser().parse_args(argv)
-    args = add_additional_params_to_args(args)
-    if not torch.cuda.is_available():
-        raise SystemExit("this tester runs on an MI355X: the HIP kernels are the only implementation (no CPU fallback)")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if not os.path.exists(args.trained_checkpoint):
-        raise OSError("%s does not exist!" % args.trained_checkpoint)
-    checkpoint = load_checkpoint(args.trained_checkpoint)
+    args = add_additional_params_to_args(get_parser().parse_args(argv))
+    dev = tester_common.device()
+    checkpoint = tester_common.load(args)
     if "args" not in checkpoint:
         raise SystemExit("%s holds no training arguments ('args'): the network and class count cannot be known" % args.trained_checkpoint)
     train_args = checkpoint["args"]
@@ -71,30 +66,19 @@ def main(argv=None):
     model = get_full_model(train_args.net, train_args.res, train_args.n_class, train_args.input_ch)
     model.load_state_dict(checkpoint["state_dict"] if "state_dict" in checkpoint else checkpoint)
     args.train_img_shape = train_args.train_img_shape
+    base_outdir = tester_common.output_dir(args)
+    tester_common.write_params(args, base_outdir)
 
-    indir, infn = os.path.split(args.trained_checkpoint)
-    trained_mode = indir.split(os.path.sep)[-2]
-    args.mode = "%s---%s-%s" % (trained_mode, args.tgt_dataset, args.split)
-    model_name = infn.replace(".pth", "")
-    base_outdir = os.path.join(args.outdir, args.mode, model_name)
-    mkdir_if_not_exist(base_outdir)
-    json_fn = os.path.join(base_outdir, "param.json")
-    check_if_done(json_fn)
-    save_dic_to_json(dict(vars(args)), json_fn, verbose=False)
-
-    train_img_shape = [int(x) for x in args.train_img_shape]
     test_img_shape = tuple(int(x) for x in args.test_img_shape)
+    train_img_shape = args.train_img_shape
     if getattr(train_args, "crop_size", -1) > 0:
-        train_img_shape = list(test_img_shape)
+        train_img_shape = test_img_shape
         print("train_img_shape was set to the same as test_img_shape")
-    spec = dict(length=args.synthetic_len, img_shape=train_img_shape, n_class=train_args.n_class, seed=args.seed) if args.synthetic else None
-    tgt_dataset = get_dataset(dataset_name=args.tgt_dataset, split=args.split, img_transform=None, label_transform=None, test=True,
-                              input_ch=train_args.input_ch, synthetic=spec)
-    loader = torch.utils.data.DataLoader(tgt_dataset, batch_size=args.batch_size, pin_memory=True)
+    loader = tester_common.make_loader(args, train_args, train_img_shape)
 
     model.to(dev)
     model.eval()
-    net = model.module if isinstance(model, torch.nn.DataParallel) else model
+    net = tester_common.unwrap(model)
     n_used = train_args.n_class if getattr(train_args, "add_bg_loss", False) else train_args.n_class - 1
 
     with open(os.path.join(base_outdir, "data_list.txt"), "w"):
@@ -102,7 +86,7 @@ def main(argv=None):
     label_root = os.path.join(base_outdir, "label")
     mkdir_if_not_exist(label_root)
     total_ent, images = 0.0, 0
-    meter = ConfusionMeter(train_args.n_class, background_id=255, device=dev)
+    meter = tester_common.new_meter(train_args, dev)
     with torch.no_grad():
         for imgs, gts, paths in loader:
             imgs = imgs.to(dev, non_blocking=True)
@@ -110,9 +94,7 @@ def main(argv=None):
             labels, ent = ops.predict_labels_up8(scores, net.up.weight, n_used)
             total_ent += float(ent) * len(paths)  # the reference's mean over images (it runs one image per batch)
             images += len(paths)
-            if torch.is_tensor(gts) and gts.dim() == 3 and tuple(gts.shape) == tuple(labels.shape):
-                gts = gts.to(dev)
-                meter.update(labels, torch.where(gts == train_args.n_class - 1, torch.full_like(gts, 255), gts))
+            tester_common.update_meter(meter, labels, gts, train_args.n_class)
             full = ops.up8(scores, net.up.weight) if args.saves_prob else None
             lab = ops.resize_u8(labels, test_img_shape, nearest=True).cpu().numpy()
             for k, path in enumerate(paths):
@@ -125,15 +107,7 @@ def main(argv=None):
                 mkdir_if_not_exist(label_outdir)
                 Image.fromarray(lab[k]).save(os.path.join(label_outdir, name))
             del full
-    ave_ent = total_ent / max(images, 1)
-    print("average entropy: %s" % ave_ent)
-    with open(os.path.join(base_outdir, "ave_ent_%s.txt" % ave_ent), "w") as f:
-        f.write(str(ave_ent))
-    if int(meter.hist.sum()) > 0:
-        summary = meter.summary()
-        save_dic_to_json(summary, os.path.join(base_outdir, "eval_result.json"), verbose=False)
-        print("pixAcc %.2f  mAcc %.2f  fwIoU %.2f  mIoU %.2f" % (summary["pixAcc"], summary["mAcc"], summary["fwIoU"], summary["mIoU"]))
-    return label_root, ave_ent
+    return label_root, tester_common.finish(base_outdir, total_ent, images, meter)
 
 
 if __name__ == "__main__":

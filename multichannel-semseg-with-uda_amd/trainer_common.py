@@ -1,12 +1,21 @@
-"""Pieces shared by the three entry scripts: process-group / device set-up, output directories, the
-optional tensorboard logger, synthetic data loaders and rank-0 checkpointing."""
+"""What the five trainers share.  ``Run`` is the process: process-group / device set-up, the optional tensorboard logger, the
+device input pipeline and rank-0 writes.  ``train`` is the one skeleton every trainer runs -- resume, output layout, loader,
+train mode, epoch loop, logging, checkpoint -- driven by a ``Trainer`` declaration of what one entry script does differently."""
+import collections
+import dataclasses
 import os
+import typing
 
 import torch
+import tqdm
 
-from datasets import ConcatDataset, get_dataset
+from argmyparse import add_additional_params_to_args
+from datasets import ConcatDataset, check_src_tgt_ok, get_dataset
+from loss import CrossEntropyLoss2d, get_prob_distance_criterion
 from mcdseg import dist as mdist
-from util import mkdir_if_not_exist, save_checkpoint, save_dic_to_json, check_if_done
+from models.model_util import fix_batchnorm_when_training, fix_dropout_when_training
+from util import (adjust_learning_rate, check_if_done, emphasize_str, get_class_weight_from_file, load_checkpoint,
+                  mkdir_if_not_exist, save_checkpoint, save_dic_to_json)
 
 
 class Run:
@@ -107,3 +116,160 @@ def make_loader(args, run, names_splits):
                                 input_ch=args.input_ch, synthetic=spec, file_list=lists[i] if i < 2 else None))
     ds = sets[0] if len(sets) == 1 else ConcatDataset(*sets)
     return torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True, pin_memory=True, drop_last=True)
+
+
+# ------------------------------------------------------------------------------------------------ the trainers' skeleton
+@dataclasses.dataclass
+class Trainer:
+    """What one entry script declares.  ``modules`` / ``optimizers`` are dicts keyed by the checkpoint key each is saved under,
+    in the order they are loaded and (the optimizers) have their learning rate adjusted."""
+    build: typing.Callable                # args -> (modules, optimizers); everything that draws from torch's RNG happens here
+    make_step: typing.Callable            # (args, run, modules, optimizers) -> step(*batch, epoch=) -> one loss per name in ``sums``
+    layout: typing.Callable               # (args, resumed) -> Layout
+    sums: tuple                           # names of the running sums, as logged
+    report: typing.Callable               # (epoch, sums, modules): rank 0's prints at the end of an epoch
+    backfill: tuple = ()                  # keys a resumed namespace may lack, beyond BACKFILL
+    on_resume: typing.Callable = None     # (pickled args, command-line args): what the command line still decides on resume
+    announces_resume: bool = False        # the two "=> load..." lines of adapt_trainer.py
+
+
+Layout = collections.namedtuple("Layout", "pth_dir tflog_dir json_fn model_name")
+
+# switches of this build that a checkpoint written before they existed does not carry
+BACKFILL = ("synthetic", "synthetic_raw", "synthetic_len", "src_file_list", "tgt_file_list", "seed", "no_pretrained", "solver", "no_tflog")
+
+
+def parse_args(parser, argv):
+    args = add_additional_params_to_args(parser.parse_args(argv))
+    if "tgt_dataset" in vars(args):
+        check_src_tgt_ok(args.src_dataset, args.tgt_dataset)
+    return args
+
+
+def resumed_args(trainer, args, cli):
+    """the pickled namespace replaces the command line's (adapt_trainer.py:40-43); the command line fills in what it lacks"""
+    if trainer.on_resume is not None:
+        trainer.on_resume(args, cli)
+    for k in trainer.backfill + BACKFILL:
+        if k not in vars(args):
+            setattr(args, k, getattr(cli, k))
+    return args
+
+
+def model_name(args, *lead):
+    return "-".join(lead + (args.savename, args.net) + (("res%s" % args.res,) if args.net in ["fcn", "psp"] else ()))
+
+
+def adapt_layout(args, resumed, mode_suffix="", method=None):
+    mode = "%s-%s2%s-%s_%sch%s" % (args.src_dataset, args.src_split, args.tgt_dataset, args.tgt_split, args.input_ch, mode_suffix)
+    name = model_name(args, method or args.method)
+    outdir = os.path.join(args.base_outdir, mode)
+    return Layout(os.path.join(outdir, "pth"), os.path.join(outdir, "tflog", name),
+                  os.path.join(outdir, "param-%s%s.json" % (name, "_resume" if resumed else "")), name)
+
+
+def checkpoint_fn(layout, epoch):
+    return os.path.join(layout.pth_dir, "%s-%s.pth.tar" % (layout.model_name, epoch))
+
+
+def held(args, modules):
+    """the modules a checkpoint holds: all of them, but F2 where ``--uses_one_classifier`` made it F1"""
+    one = getattr(args, "uses_one_classifier", False)
+    return {key: m for key, m in modules.items() if not (one and key == "f2_state_dict")}
+
+
+def checkpoint_dict(args, epoch, modules, optimizers):
+    dic = {"epoch": epoch, "args": args}
+    dic.update((key, m.state_dict()) for key, m in list(held(args, modules).items()) + list(optimizers.items()))
+    return dic
+
+
+def criteria(args, device=None, cross_entropy=CrossEntropyLoss2d):
+    """(cross entropy under the class weights, the ``--d_loss`` discrepancy; symkl needs the row length -- the reference passes none
+    and fails there)"""
+    weight = get_class_weight_from_file(n_class=args.n_class, weight_filename=args.loss_weights_file, add_bg_loss=args.add_bg_loss)
+    return cross_entropy(weight if device is None else weight.to(device)), get_prob_distance_criterion(args.d_loss, n_class=args.n_class)
+
+
+def mcd_report(epoch, sums, modules):
+    print("Epoch [%d] DLoss: %.4f CLoss: %.4f" % (epoch, sums["d_loss"], sums["c_loss"]))
+
+
+def _resume_or_build(trainer, run, cli):
+    if not cli.resume:
+        return (cli,) + tuple(trainer.build(cli)) + (0,)
+    if trainer.announces_resume:
+        print("=> loading checkpoint '{}'".format(cli.resume))
+    if not os.path.exists(cli.resume):
+        raise OSError("%s does not exist!" % cli.resume)
+    checkpoint = load_checkpoint(cli.resume)
+    args = resumed_args(trainer, checkpoint["args"], cli)
+    modules, optimizers = trainer.build(args)
+    for key, m in held(args, modules).items():
+        m.load_state_dict(checkpoint[key])
+    for m in modules.values():
+        m.to(run.device)
+    for key, optimizer in optimizers.items():
+        optimizer.load_state_dict(checkpoint[key])
+    if trainer.announces_resume:
+        print("=> loaded checkpoint '{}'".format(args.resume))
+    return args, modules, optimizers, checkpoint["epoch"]
+
+
+def train(trainer, args):
+    """``args`` as ``parse_args`` returns them.  ``Run`` seeds torch, then the models are built, then the loader is made: the initial
+    weights and the shuffle order depend on that order."""
+    run = Run(args)
+    resumed = bool(args.resume)
+    args, modules, optimizers, start_epoch = _resume_or_build(trainer, run, args)
+    if getattr(args, "uses_one_classifier", False) and "f2_state_dict" in modules:
+        print("f1 and f2 are same!")
+        modules["f2_state_dict"] = modules["f1_state_dict"]
+
+    layout = trainer.layout(args, resumed)
+    if run.is_main:
+        mkdir_if_not_exist(layout.pth_dir)
+    run.configure_logger(layout.tflog_dir, args)
+    run.save_params(args, layout.json_fn)
+
+    adapt = "tgt_dataset" in vars(args)  # (source, target) pairs and the per-iteration line, or one dataset
+    train_loader = make_loader(args, run, [(args.src_dataset, args.src_split), (args.tgt_dataset, args.tgt_split)] if adapt
+                               else [(args.src_dataset, args.split)])
+    for m in modules.values():
+        m.to(run.device)
+    run.sync_replicas(list(modules.values()))
+    for m in modules.values():
+        m.train()
+    if args.no_dropout:
+        for m in modules.values():
+            fix_dropout_when_training(m)
+    if args.fix_bn:
+        emphasize_str("BN layers are NOT trained!")
+        for m in modules.values():
+            fix_batchnorm_when_training(m)
+    step = trainer.make_step(args, run, modules, optimizers)
+
+    for epoch in range(start_epoch, args.epochs):
+        sums = dict.fromkeys(trainer.sums, 0.0)
+        it = enumerate(train_loader)
+        for ind, batch in (tqdm.tqdm(it) if run.is_main else it):
+            source, *targets = batch if adapt else (batch,)
+            losses = step(run.images(source[0]), run.labels(source[1]), *(run.images(t[0]) for t in targets), epoch=epoch)
+            losses = dict(zip(trainer.sums, (float(v) for v in losses)))
+            for name, value in losses.items():
+                sums[name] += value
+            if adapt and ind % 100 == 0 and run.is_main:
+                print("iter [%d] DLoss: %.6f CLoss: %.4f" % (ind, losses["d_loss"], losses["c_loss"]))
+            if ind > args.max_iter:
+                break
+        if run.is_main:
+            trainer.report(epoch, sums, modules)
+        for name in trainer.sums:
+            run.log_value(name, sums[name], epoch)
+        run.log_value("lr", args.lr, epoch)
+        if args.adjust_lr:  # the reference passes weight_decay as the decay rate (adapt_trainer.py:228-230)
+            for optimizer in optimizers.values():
+                args.lr = adjust_learning_rate(optimizer, args.lr, args.weight_decay, epoch, args.epochs)
+        args.start_epoch = epoch + 1
+        run.save(checkpoint_dict(args, epoch + 1, modules, optimizers), checkpoint_fn(layout, epoch + 1))
+    return 0

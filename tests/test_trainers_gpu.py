@@ -109,6 +109,39 @@ def test_adapt_multitask_trainer(tmp_path):
     assert list(ck["dec_state_dict"]["deprgr_dec.conv3.weight"].shape) == [3, 512, 1, 1]
 
 
+RESUMES = {  # script: (its own flags, output directory, checkpoint name without "-<epoch>.pth.tar", the state dict of the first module)
+    "adapt_mfnet_trainer": (["suncg", "nyu", "--method_detail", "MFNet-ScoreAddFusion"], "suncg-train2nyu-train_6ch_MFNet",
+                            "MFNet-ScoreAddFusion-normal-drn_d_22", "g_3ch_state_dict"),
+    "adapt_multitask_trainer": (["suncg", "nyu"], "suncg-train2nyu-train_6ch_MCDmultitask", "MCD-normal-drn_d_22", "enc_state_dict"),
+    "source_trainer": (["suncg"], "suncg-train_only_6ch", "normal-drn_d_22", "state_dict"),
+}
+
+
+@pytest.mark.parametrize("name", sorted(RESUMES))
+def test_trainer_resumes_from_its_checkpoint(tmp_path, name):
+    """one epoch, then one more from the checkpoint under the checkpoint's arguments: the second checkpoint has the first one's layout,
+    and the first BatchNorm layer has seen exactly as many batches again -- the state was loaded, not rebuilt"""
+    _need_gpu()
+    import importlib
+    import util
+    trainer = importlib.import_module(name)
+    own, mode, model_name, first = RESUMES[name]
+    pth = os.path.join(str(tmp_path / "out"), mode, "pth")
+    assert trainer.main(own + ["--base_outdir", str(tmp_path / "out"), "--net", "drn_d_22"] + COMMON) == 0
+    ck_fn = os.path.join(pth, model_name + "-1.pth.tar")
+    ck = util.load_checkpoint(ck_fn)
+    bn = next(k for k in ck[first] if k.endswith("num_batches_tracked"))
+    assert bn.endswith("base.0.1.num_batches_tracked") and int(ck[first][bn]) > 0 and ck["epoch"] == 1
+    ck["args"].epochs = 2
+    util.save_checkpoint(ck, False, ck_fn)
+    assert trainer.main(own + ["--resume", ck_fn] + COMMON) == 0
+    ck2_fn = os.path.join(pth, model_name + "-2.pth.tar")
+    assert os.path.exists(ck2_fn)
+    ck2 = util.load_checkpoint(ck2_fn)
+    assert ck2["epoch"] == 2 and sorted(ck2.keys()) == sorted(ck.keys())
+    assert int(ck2[first][bn]) == 2 * int(ck[first][bn])
+
+
 def test_adapt_tester_label_maps_match_oracle(tmp_path):
     """Train one synthetic epoch, run the tester (folded-BN inference + argmax/entropy kernel) and compare the written
     label PNGs and the entropy with the CPU oracle evaluating the same checkpoint (adapt_tester.py:87-126)."""
