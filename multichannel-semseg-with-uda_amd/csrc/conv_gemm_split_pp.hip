@@ -30,6 +30,13 @@
 //   * at the end of its read phase of step s a group waits vmcnt(share) -- everything but the share just issued -- so its share
 //     of step s+1 has landed before the barrier; group 1 passes that barrier at the end of interval 2s+1, and the first read of
 //     step s+1 is group 0's in interval 2s+2.
+//
+// Dead taps (option SKIP_DEAD_TAPS, default 1).  A pixel tile whose every pixel has tap q in the zero padding -- the 256 x 320 tile is
+// four rows of an 80-wide map, so with dilation 4 the first tile of an image has the three taps ky = 0 there and the last the three
+// taps ky = 2 -- spends that tap's K-steps staging weights and multiplying them by zeros.  The kernel ORs valid_mask over the
+// workgroup (one barrier in the prologue) and its loader steps over the taps no pixel uses; the surviving steps keep their K order
+// and their weight slabs, so outputs and BatchNorm partial rows are bit for bit those of the full loop.  The one difference: a
+// weight that is Inf or NaN gave NaN (Inf * 0) in a skipped step of the full loop, and contributes nothing here.
 #include <cstdlib>
 #include <type_traits>
 
@@ -156,7 +163,33 @@ __global__ __launch_bounds__(512, (WM * WN <= 4 ? 4 : 2)) void conv_gemm_split_p
     a_voff[i] = id < A_UNITS ? ((unsigned)plane * (unsigned)p.Mp + (unsigned)m) * 16u : OOB;
   }
 
-  // loader state: K order is channel-chunk outer, tap inner (the shifted re-reads of a 16-channel slab are back to back)
+  // ---- the tile's LIVE taps (option SKIP_DEAD_TAPS): the OR of valid_mask over the whole workgroup.  A tap whose bit is clear lies
+  // in the zero padding for every pixel of the tile -- every pixel-operand DMA of its K-steps would deposit zeros -- so the loader
+  // steps over it.  One mask per WORKGROUP, not per wave: the counted waits and the barrier pairing of the two groups need every wave
+  // to run the same number of steps.  Wave OR, then the eight waves' words through the head of stage 2, which no DMA targets before
+  // the prologue's closing barrier -- and every wave has read the words by then: it needs the mask to issue its first DMA.
+  const unsigned all_taps = taps >= 32 ? 0xFFFFFFFFu : (1u << taps) - 1u;
+  unsigned live = all_taps;
+  if (p.skip_dead) {
+    unsigned m = 0;
+#pragma unroll
+    for (int x = 0; x < NPX; ++x) m |= valid_mask[x];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m |= __shfl_xor(m, o, 64);
+    volatile unsigned* live_w = reinterpret_cast<volatile unsigned*>(As + 2 * A_BYTES);
+    if (lane == 0) live_w[wave] = m;
+    __syncthreads();
+    m = 0;
+#pragma unroll
+    for (int w = 0; w < NT / 64; ++w) m |= live_w[w];
+    m = __builtin_amdgcn_readfirstlane(m);
+    // all taps when none is live (a tile past the pixels: the loop still runs, on zeros) or when the live steps do not pair up
+    const int live_steps = __builtin_popcount(m) * (p.Kp / 16);
+    if (m != 0 && (KDEEP == 1 || (live_steps % KDEEP) == 0)) live = m;
+  }
+
+  // loader state: K order is channel-chunk outer, tap inner (the shifted re-reads of a 16-channel slab are back to back); l_kstep is
+  // the step's number among ALL steps, dead ones included: the index of its weight slab
   int l_tap = 0, l_c0 = 0, l_ky = 0, l_kx = 0, l_kstep = 0;
   auto issue_sub = [&](int buf, int d) {  // this wave's share of one K-step: A_DMAS KB of the weight slab, NPU x 1 KB of gathered pixel units
 #if defined(__HIP_DEVICE_COMPILE__)  // the LDS address space does not exist in the host pass of this translation unit
@@ -192,7 +225,7 @@ __global__ __launch_bounds__(512, (WM * WN <= 4 ? 4 : 2)) void conv_gemm_split_p
     (void)d;
 #endif
   };
-  auto advance = [&]() {
+  auto next_step = [&]() {
     ++l_kstep;
     ++l_tap;
     if (++l_kx == p.KW) {
@@ -206,6 +239,11 @@ __global__ __launch_bounds__(512, (WM * WN <= 4 ? 4 : 2)) void conv_gemm_split_p
       l_c0 += 16;
     }
   };
+  auto advance = [&]() {  // to the next live step (scalar: `live` is workgroup-uniform and never empty)
+    do next_step();
+    while (((live >> l_tap) & 1u) == 0);
+  };
+  while (((live >> l_tap) & 1u) == 0) next_step();  // the first live tap of the first channel chunk
 
   auto issue = [&](int buf) {  // one barrier interval's operands: KDEEP consecutive K-steps
     issue_sub(buf, 0);
@@ -226,7 +264,8 @@ __global__ __launch_bounds__(512, (WM * WN <= 4 ? 4 : 2)) void conv_gemm_split_p
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  const int nsteps = taps * (p.Kp / 16) / KDEEP;  // (KDEEP > 1: the host launches this instantiation for an even number of K-steps only)
+  // (KDEEP > 1: the host launches this instantiation for an even number of K-steps only; `live` is all taps where its steps are odd)
+  const int nsteps = __builtin_popcount(live) * (p.Kp / 16) / KDEEP;
   issue(0);
   if (nsteps > 1) {
     advance();
@@ -661,6 +700,7 @@ int mcdseg_internal_conv_pp_rest(const ConvSplitParams& p, int math, bool dgrad)
 int mcdseg_internal_conv_pp_launch(const ConvSplitParams& p, int math, bool dgrad, int64_t pixels, hipStream_t st) {
   ConvSplitParams q = p;
   q.sub = 0;
+  q.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
   q.tile_n0 = 0;
   if (const int kind = pp_wide(p, math, dgrad)) {
     q.tile_n1 = ceil_div(p.P, kind == 3 ? 160 : 320);
@@ -683,6 +723,7 @@ int mcdseg_internal_conv_pp_launch(const ConvSplitParams& p, int math, bool dgra
 int mcdseg_internal_conv_pp_rest_launch(const ConvSplitParams& p, int math, bool dgrad, int64_t pix0, hipStream_t st) {
   ConvSplitParams q = p;
   q.sub = 0;
+  q.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
   q.tile_n0 = (int)(pix0 / 128);
   q.tile_n1 = ceil_div(p.P, 128);
   launch_math<2, 2, 2, 2>(q, math, dgrad, st);

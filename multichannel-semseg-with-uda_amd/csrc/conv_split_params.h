@@ -45,6 +45,9 @@ struct ConvSplitParams {
   void* dst16;
   float* dst_bound;
   const void* ep_res16;
+  // ping-pong kernel: 1 = the loader steps over the taps that lie in the zero padding for every pixel of the tile (option
+  // SKIP_DEAD_TAPS, set by the launchers of conv_gemm_split_pp.hip at every call)
+  int skip_dead;
 };
 
 typedef _Float16 mcd_f16x4 __attribute__((ext_vector_type(4)));

@@ -23,6 +23,12 @@
 // 256 x 256 accumulators to slab number  g / L + g / KT  (g = the segment's first flattened K-step; the numbers of a tile's segments
 // are consecutive), and wgrad_reduce_sk_kernel sums a tile's slabs in K order in fp64 -- a fixed order, so the result is reproducible --
 // and applies scale(x) * scale(dz).
+//
+// Dead rows (option SKIP_DEAD_TAPS, default 1).  For a tap with ky * dil < pad the first output rows of every image read input rows
+// above the image, for one with ky * dil > pad the last ones read rows below it: the X operand of those K-steps is all zeros.  Both
+// kernels here walk the live rows of every image only (the row-of-taps kernel: the rows of its kernel row ky); the surviving steps
+// keep their order and a slab of dead steps only is written as zeros, so the slab reduction adds what it added before, bit for bit.
+// The one difference: an Inf or NaN in dZ gave NaN (Inf * 0) in a skipped step of the full loop, and contributes nothing here.
 #include <cstdlib>
 #include <type_traits>
 
@@ -44,6 +50,45 @@ struct WgradPpParams {
   int items;               // slabs * tiles
   int x_cb_bytes, dy_cb_bytes;                // ONE piece of each companion (this call's images)
   long long x_piece_stride, dy_piece_stride;  // bytes between the pieces (the companions' own batch: mcdseg_conv_desc.Ncb)
+  int skip_dead;  // 1 = a tile's loader steps over the output rows whose shifted input row lies in the zero padding (option SKIP_DEAD_TAPS)
+};
+
+// Dead rows (option SKIP_DEAD_TAPS): output row ty of a tile's kernel row ky reads input row ty * stride + ky * dil - pad; where that lies
+// outside the image every X unit of the row's K-steps is a zero deposited by the range check, and the steps add dZ * 0.  The live rows
+// are lo .. hi - 1 of every image and the loader walks those only.  All of it follows from the tile and the slab alone -- the same in
+// every wave, before the loop -- so the step count that the counted waits, the stage ring and the barrier pairing rest on stays
+// uniform.  (Rows only: a 16-pixel run is never wholly outside the image by its columns alone.)
+struct LiveRows {
+  int lo, hi, tiles_x, ntiles;
+  __device__ LiveRows(const WgradPpParams& p, int ky) : lo(0), hi(p.tiles_y), tiles_x(p.tiles_x), ntiles(p.tiles_x * p.tiles_y) {
+    if (!p.skip_dead) return;
+    const int sh = ky * p.dil - p.pad;  // (the X operand's row shift: also in the waves that move dZ)
+    if (sh < 0) lo = (-sh + p.stride - 1) / p.stride;
+    const int last = p.H - 1 - sh;  // the largest ty * stride that still reads inside the image
+    const int h = last < 0 ? 0 : last / p.stride + 1;
+    if (h < hi) hi = h;
+    if (lo > hi) lo = hi;
+  }
+  __device__ int before(int k) const {  // live K-steps among steps 0 .. k - 1 of a tile
+    const int n = k / ntiles;
+    const int ty = (k - n * ntiles) / tiles_x;
+    const int tx = k - n * ntiles - ty * tiles_x;
+    const int done = ty < lo ? 0 : (ty < hi ? ty - lo : hi - lo);
+    return (n * (hi - lo) + done) * tiles_x + (ty >= lo && ty < hi ? tx : 0);
+  }
+  __device__ void first(int k, int& n, int& ty, int& tx) const {  // the first live step at or behind step k: (image, output row, column block)
+    n = k / ntiles;
+    ty = (k - n * ntiles) / tiles_x;
+    tx = k - n * ntiles - ty * tiles_x;
+    if (ty < lo) {
+      ty = lo;
+      tx = 0;
+    } else if (ty >= hi) {
+      ty = lo;
+      tx = 0;
+      ++n;
+    }
+  }
 };
 
 template <class P>
@@ -182,9 +227,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
     for (int d = 0; d < NDMA; ++d) vconst[d] = (cg0 + d + 4 * cgl) < sC8 ? (unsigned)((d + 4 * cgl) * sHW + px * sS) * 16u : OOB;
 
     // loader state: K-step -> (image, output row, 16-pixel column block), advanced incrementally
-    int l_n = k0 / ntiles;
-    int l_ty = (k0 - l_n * ntiles) / p.tiles_x;
-    int l_tx = k0 - l_n * ntiles - l_ty * p.tiles_x;
+    const LiveRows rows(p, ky);  // (option SKIP_DEAD_TAPS: the loader walks the rows whose shifted input row lies inside the image)
+    int l_n, l_ty, l_tx;
+    rows.first(k0, l_n, l_ty, l_tx);
     auto stage_off = [](int c) { return DEEP ? (c < NS ? c * STAGE : (c - NS) * STAGE + UNIT) : c * STAGE; };
     auto issue = [&](int stage) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -206,8 +251,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
     auto advance = [&]() {
       if (++l_tx == p.tiles_x) {
         l_tx = 0;
-        if (++l_ty == p.tiles_y) {
-          l_ty = 0;
+        if (++l_ty == rows.hi) {
+          l_ty = rows.lo;
           ++l_n;
         }
       }
@@ -221,8 +266,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int nsteps = k1 - k0;
-    issue(0);
+    const int nsteps = rows.before(k1) - rows.before(k0);  // (0 where every row of the slab is dead: the item's sums are zeros)
+    if (nsteps > 0) issue(0);
 #pragma unroll
     for (int a = 1; a < PRO; ++a)
       if (nsteps > a) {
@@ -514,9 +559,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
 #pragma unroll
     for (int d = 0; d < NDMA; ++d) vconst[d] = (cg0 + d + 4 * cgl) < sC8 ? (unsigned)((d + 4 * cgl) * sHW + px * sS) * 16u : OOB;
 
-    int l_n = k0 / ntiles;
-    int l_ty = (k0 - l_n * ntiles) / p.tiles_x;
-    int l_tx = k0 - l_n * ntiles - l_ty * p.tiles_x;
+    const LiveRows rows(p, ky);  // (option SKIP_DEAD_TAPS: the loader walks the rows whose shifted input row lies inside the image)
+    int l_n, l_ty, l_tx;
+    rows.first(k0, l_n, l_ty, l_tx);
     auto issue = [&](int stage) {
 #if defined(__HIP_DEVICE_COMPILE__)
       if (dma_on) {
@@ -537,8 +582,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
     auto advance = [&]() {
       if (++l_tx == p.tiles_x) {
         l_tx = 0;
-        if (++l_ty == p.tiles_y) {
-          l_ty = 0;
+        if (++l_ty == rows.hi) {
+          l_ty = rows.lo;
           ++l_n;
         }
       }
@@ -552,8 +597,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    const int nsteps = k1 - k0;
-    issue(0);
+    const int nsteps = rows.before(k1) - rows.before(k0);  // (0 where every row of the slab is dead: the item's sums are zeros)
+    if (nsteps > 0) issue(0);
     if (nsteps > 1) {
       advance();
       issue(1);
@@ -749,6 +794,7 @@ int mcdseg_internal_wgrad_pp_launch(const mcdseg_conv_desc* d, int math, const v
   p.tiles_x = ceil_div(d->Wo, 16); p.tiles_y = d->Ho;
   p.kt = d->N * p.tiles_x * p.tiles_y;
   p.L = L; p.nwg = nwg;
+  p.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
   p.slabs = slabs; p.items = slabs * p.co_tiles * p.ci_tiles * d->KH * d->KW;
   p.x_cb_bytes = (int)xb; p.dy_cb_bytes = (int)yb;
   p.x_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cin * d->H * d->W * 2;  // (F16X1 reads piece 0 only)
@@ -824,6 +870,7 @@ int mcdseg_internal_wgrad_pp3_launch(const mcdseg_conv_desc* d, int math, const 
   p.tiles_x = ceil_div(d->Wo, 16); p.tiles_y = d->Ho;
   p.kt = d->N * p.tiles_x * p.tiles_y;
   p.L = L; p.nwg = nwg;
+  p.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
   p.slabs = slabs; p.items = slabs * p.co_tiles * p.ci_tiles * d->KH;
   p.x_cb_bytes = (int)xb; p.dy_cb_bytes = (int)yb;
   p.x_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cin * d->H * d->W * 2;  // (F16X1 reads piece 0 only)

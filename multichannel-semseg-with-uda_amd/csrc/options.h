@@ -19,6 +19,7 @@
   X(PP_WIDE_FILL, 80)         /* per cent of its rounds the 320-pixel tile must fill (> 100 = never) */                      \
   X(PP_WIDE128, 1)            /* the 128 x 320 variant */                                                                    \
   X(PP_DEEP, 1)               /* one-term arithmetic: two K-steps per barrier interval of the ping-pong kernels (SplitF16x1D) */ \
+  X(SKIP_DEAD_TAPS, 1)        /* ping-pong kernels step over the K-steps whose taps lie wholly in the zero padding (0 = every step) */ \
   X(THIN_WINDOW, 1)           /* LDS-window kernels of the thin 3x3 layers */                                                \
   X(WGRAD_WGS, 1024)          /* target workgroup count of the 128 / 64-tile weight-gradient plans */                        \
   X(WGRAD_THIN_TR, 1)         /* thin layers' window weight gradient */                                                      \
