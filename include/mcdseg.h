@@ -211,7 +211,8 @@ int mcdseg_conv_wgrad(const mcdseg_conv_desc* d, const float* x, const float* dy
  * y_bound (may be NULL): receives an upper bound of |y| for the tensor mcdseg_bn_apply(_cb) is about to write from these
  * statistics, y = act(gamma*xhat + beta (+ residual)): max_c(|gamma_c| sqrt(n-1) + |beta_c|) + res_bound[0], using
  * Samuelson's inequality |xhat| <= sqrt(n-1) for a batch of n values normalised by their own mean and biased variance
- * (gamma, beta required then; res_bound = bound scalar of the residual tensor or NULL). */
+ * (gamma, beta required then; res_bound = bound scalar of the residual tensor or NULL).  The inequality needs z to be the very
+ * tensor the statistics came from, so the bound is valid in train mode only: eval mode (running statistics) has no such bound. */
 size_t mcdseg_bn_stats_workspace_bytes(int64_t rows, int32_t C);
 int mcdseg_bn_stats_finalize(const float* stat_partials, int64_t rows, int32_t C, int32_t Mp,
                              float* mean, float* rstd, float* running_mean, float* running_var,
@@ -252,8 +253,9 @@ int mcdseg_bn_bwd_apply_cb(const float* dy, const float* y, const void* y_cb, co
                            void* dz_cb, const float* dz_bound, int32_t math, int32_t N, int32_t C, int32_t HW, int32_t relu,
                            int32_t train, void* stream);
 /* The backward pair for a ReLU group WITHOUT a residual branch (models/drn.py:43-47 bn1; the conv-BN-ReLU chains of
- * _make_conv_layers): the mask y > 0 is recomputed from z -- y > 0 <=> fma(z, gamma rstd, beta - mean gamma rstd) > 0, which is the
- * forward kernels' own expression, bit for bit -- so y is not read at all: 8 instead of 12 bytes per element in the reduce, 12
+ * _make_conv_layers): the mask y > 0 is recomputed from z -- y > 0 <=> fma(z, gamma rstd, beta - mean gamma rstd) > 0 (with the mean
+ * subtracted from z first in a channel whose |mean| rstd exceeds 8: csrc/bn.hip, bn_forward_map), which is the forward kernels' own
+ * expression, bit for bit -- so y is not read at all: 8 instead of 12 bytes per element in the reduce, 12
  * instead of 16 in the apply.  Same results as mcdseg_bn_bwd_reduce / mcdseg_bn_bwd_apply_cb with relu = 1 and the group's fp32 y. */
 int mcdseg_bn_bwd_reduce_zmask(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
                                const float* beta, float* dgamma, float* dbeta, float* dz_bound, int32_t train, int32_t N, int32_t C,

@@ -232,6 +232,26 @@ __global__ void bn_eval_affine_kernel(const float* __restrict__ gamma, const flo
 }
 
 // ------------------------------------------------------------------------------------------------
+// The forward map of one channel, y = gamma (z - mean) rstd + beta, as y = fma(z - m0, a, b0) with a = gamma rstd and
+//   (m0, b0) = (0, beta - mean a)   while |mean| rstd <= BN_CENTRE_RATIO: z - 0 is z, so this is fma(z, a, beta - mean a), one rounding
+//                                   of the affine map.  b0 and the product z a are of the size of mean a, and each is rounded there: an
+//                                   error of 2 x 2^-24 |mean| rstd |gamma| at the most -- 1e-6 |gamma| at the ratio 8, four ulp of a
+//                                   normalised value of order one;
+//   (m0, b0) = (mean, beta)         beyond it: the subtraction comes first -- exact wherever z lies within a factor of two of the mean --
+//                                   and nothing of the size of mean a is rounded.  (At |mean|/std = 1e3 the first form costs
+//                                   2e-5 .. 8e-5 |gamma| where this one keeps 1e-6: docs/MEASURED_HISTORY.md.)
+// The choice is per channel, from the fp32 mean and rstd every kernel is handed: every kernel that forms y or recomputes y > 0 from z
+// goes through this function, so they agree bit for bit.  (A NaN statistic takes the first form and shows in y either way.)
+#ifndef BN_CENTRE_RATIO
+#define BN_CENTRE_RATIO 8.f
+#endif
+__device__ __forceinline__ void bn_forward_map(float gamma, float beta, float mean, float rstd, float& a, float& m0, float& b0) {
+  a = gamma * rstd;
+  const bool centred = fabsf(mean * rstd) > BN_CENTRE_RATIO;
+  m0 = centred ? mean : 0.f;
+  b0 = centred ? beta : beta - mean * a;
+}
+
 // apply: grid.x = plane (n*C + c), grid.y = chunk of the plane; float4 when HW % 4 == 0.
 template <bool VEC>
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ z, const float* __restrict__ mean,
@@ -240,8 +260,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
                                                        float* __restrict__ y, int C, int HW, int relu) {
   const int plane = blockIdx.x;
   const int c = plane % C;
-  const float a = gamma[c] * rstd[c];
-  const float b = beta[c] - mean[c] * a;
+  float a, mu, b;  // y = fma(z - mu, a, b)
+  bn_forward_map(gamma[c], beta[c], mean[c], rstd[c], a, mu, b);
   const size_t base = (size_t)plane * HW;
   if (VEC) {
     const int n4 = HW >> 2;
@@ -250,7 +270,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     float4* y4 = reinterpret_cast<float4*>(y + base);
     for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < n4; i += gridDim.y * blockDim.x) {
       float4 v = z4[i];
-      v.x = fmaf(v.x, a, b); v.y = fmaf(v.y, a, b); v.z = fmaf(v.z, a, b); v.w = fmaf(v.w, a, b);
+      v.x = fmaf(v.x - mu, a, b); v.y = fmaf(v.y - mu, a, b); v.z = fmaf(v.z - mu, a, b); v.w = fmaf(v.w - mu, a, b);
       if (r4) {
         const float4 q = r4[i];
         v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
@@ -262,7 +282,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     }
   } else {
     for (int i = blockIdx.y * blockDim.x + threadIdx.x; i < HW; i += gridDim.y * blockDim.x) {
-      float v = fmaf(z[base + i], a, b);
+      float v = fmaf(z[base + i] - mu, a, b);
       if (res) v += res[base + i];
       if (relu) v = fmaxf(v, 0.f);
       y[base + i] = v;
@@ -322,11 +342,11 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
   if (dz_bound != nullptr && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *dz_bound = 0.f;  // finalize: atomic max
   const float mu = z ? mean[c] : 0.f;
   const float rs = z ? rstd[c] : 0.f;
-  // ReLU mask without reading y (mbeta != NULL; a group WITHOUT residual): y > 0 <=> fma(z, a, b) > 0 with the forward kernels'
-  // own a = gamma rstd, b = beta - mean a (bn_apply_kernel / bn_apply_cb_kernel: the same expressions, bit for bit)
+  // ReLU mask without reading y (mbeta != NULL; a group WITHOUT residual): y > 0 <=> fma(z - m0, a, b0) > 0 with the forward
+  // kernels' own map (bn_forward_map: the same expressions, bit for bit)
   constexpr bool zm = MASK == 2;
-  const float ma = zm ? mgamma[c] * rs : 0.f;
-  const float mb = zm ? mbeta[c] - mu * ma : 0.f;
+  float ma = 0.f, mm = 0.f, mb = 0.f;
+  if (zm) bn_forward_map(mgamma[c], mbeta[c], mu, rs, ma, mm, mb);
   float s_dy = 0.f, s_dyx = 0.f, m_g = 0.f;
   const int items = N * cpp;
   for (int item = blockIdx.y; item < items; item += S) {
@@ -380,8 +400,8 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
             g.x = ((w0 >> lane) & 1ull) ? g.x : 0.f; g.y = ((w1 >> lane) & 1ull) ? g.y : 0.f;
             g.z = ((w2 >> lane) & 1ull) ? g.z : 0.f; g.w = ((w3 >> lane) & 1ull) ? g.w : 0.f;
           } else if (MASK == 2) {
-            g.x = fmaf(v.x, ma, mb) > 0.f ? g.x : 0.f; g.y = fmaf(v.y, ma, mb) > 0.f ? g.y : 0.f;
-            g.z = fmaf(v.z, ma, mb) > 0.f ? g.z : 0.f; g.w = fmaf(v.w, ma, mb) > 0.f ? g.w : 0.f;
+            g.x = fmaf(v.x - mm, ma, mb) > 0.f ? g.x : 0.f; g.y = fmaf(v.y - mm, ma, mb) > 0.f ? g.y : 0.f;
+            g.z = fmaf(v.z - mm, ma, mb) > 0.f ? g.z : 0.f; g.w = fmaf(v.w - mm, ma, mb) > 0.f ? g.w : 0.f;
           } else if (MASK == 1) {
             const float4 o = oq[u];
             g.x = o.x > 0.f ? g.x : 0.f; g.y = o.y > 0.f ? g.y : 0.f;
@@ -398,7 +418,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const float* __restr
       for (int i = e0 + threadIdx.x; i < e1; i += 256) {
         float g = dy[base + i];
         if (MASK == 2) {
-          if (!(fmaf(z[base + i], ma, mb) > 0.f)) g = 0.f;
+          if (!(fmaf(z[base + i] - mm, ma, mb) > 0.f)) g = 0.f;
         } else if (MASK == 1 && !(y[base + i] > 0.f)) {
           g = 0.f;
         }
@@ -584,12 +604,11 @@ __global__ __launch_bounds__(256) void bn_apply_cb_kernel(const float* __restric
   const int g = ng % C8;
   const int n = ng / C8;
   const float inv_scale = 1.f / operand_scale<P>(y_bound);
-  float ca[8], cbeta[8];
+  float ca[8], cmu[8], cbeta[8];  // y = fma(z - cmu, ca, cbeta): bn_forward_map
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = 8 * g + e;
-    ca[e] = gamma[c] * rstd[c];
-    cbeta[e] = beta[c] - mean[c] * ca[e];
+    bn_forward_map(gamma[c], beta[c], mean[c], rstd[c], ca[e], cmu[e], cbeta[e]);
   }
 #pragma unroll
   for (int it = 0; it < BN_PIX_ITERS; ++it) {
@@ -601,7 +620,7 @@ __global__ __launch_bounds__(256) void bn_apply_cb_kernel(const float* __restric
     float v[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      float t = fmaf(z[base + (size_t)e * HW], ca[e], cbeta[e]);
+      float t = fmaf(z[base + (size_t)e * HW] - cmu[e], ca[e], cbeta[e]);
       if (res) t += res[base + (size_t)e * HW];
       if (res_cb != nullptr) t += r[e];
       if (relu) t = fmaxf(t, 0.f);
@@ -659,12 +678,11 @@ __global__ __launch_bounds__(BN_V4_NT) void bn_apply_cb_v4_kernel(const float* _
   const int g = ng % C8;
   const int n = ng / C8;
   const float inv_scale = 1.f / operand_scale<P>(y_bound);
-  float ca[8], cbeta[8];
+  float ca[8], cmu[8], cbeta[8];  // y = fma(z - cmu, ca, cbeta): bn_forward_map
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = 8 * g + e;
-    ca[e] = gamma[c] * rstd[c];
-    cbeta[e] = beta[c] - mean[c] * ca[e];
+    bn_forward_map(gamma[c], beta[c], mean[c], rstd[c], ca[e], cmu[e], cbeta[e]);
   }
   const int wave = threadIdx.x >> 6;
   const int pix_wave = (bx * BN_V4_NT + 64 * wave) * 4;  // first pixel of this wave's 256
@@ -688,8 +706,8 @@ __global__ __launch_bounds__(BN_V4_NT) void bn_apply_cb_v4_kernel(const float* _
     for (int e = 0; e < 8; ++e) {
       const float4 zv = zq[e];
       float4 t;
-      t.x = fmaf(zv.x, ca[e], cbeta[e]); t.y = fmaf(zv.y, ca[e], cbeta[e]);
-      t.z = fmaf(zv.z, ca[e], cbeta[e]); t.w = fmaf(zv.w, ca[e], cbeta[e]);
+      t.x = fmaf(zv.x - cmu[e], ca[e], cbeta[e]); t.y = fmaf(zv.y - cmu[e], ca[e], cbeta[e]);
+      t.z = fmaf(zv.z - cmu[e], ca[e], cbeta[e]); t.w = fmaf(zv.w - cmu[e], ca[e], cbeta[e]);
       if (RES == 1) {
         const float4 rv = rq[e];
         t.x += rv.x; t.y += rv.y; t.z += rv.z; t.w += rv.w;
@@ -739,14 +757,18 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cb_kernel(const float* __res
   const float inv_scale = 1.f / operand_scale<P>(dz_bound);
   const float inv_n = 1.f / ((float)N * (float)HW);
   const bool zm = relu && mbeta != nullptr;  // mask from z (see bn_bwd_reduce_kernel): y is not read
-  float cmu[8], crs[8], ca[8], k1[8], k2[8], cmb[8];
+  float cmu[8], crs[8], ca[8], k1[8], k2[8], cm0[8], cmb[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = 8 * g + e;
     cmu[e] = mean[c];
     crs[e] = rstd[c];
     ca[e] = gamma[c] * crs[e];
-    cmb[e] = zm ? mbeta[c] - cmu[e] * ca[e] : 0.f;
+    cm0[e] = cmb[e] = 0.f;
+    if (zm) {  // the forward kernels' own map for the mask (bn_forward_map gives the same a = gamma rstd)
+      float fa;
+      bn_forward_map(gamma[c], mbeta[c], cmu[e], crs[e], fa, cm0[e], cmb[e]);
+    }
     k1[e] = train ? dbeta[c] * inv_n : 0.f;
     k2[e] = train ? dgamma[c] * inv_n : 0.f;
   }
@@ -762,7 +784,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_cb_kernel(const float* __res
       float gv = dy[base + (size_t)e * HW];
       const float zv = z[base + (size_t)e * HW];
       if (zm) {
-        if (!(fmaf(zv, ca[e], cmb[e]) > 0.f)) gv = 0.f;
+        if (!(fmaf(zv - cm0[e], ca[e], cmb[e]) > 0.f)) gv = 0.f;
       } else if (relu && (y != nullptr ? !(y[base + (size_t)e * HW] > 0.f) : !((ymask >> e) & 1u))) {
         gv = 0.f;
       }
@@ -798,14 +820,18 @@ __global__ __launch_bounds__(BN_V4_NT) void bn_bwd_apply_cb_v4_kernel(const floa
   const float inv_scale = 1.f / operand_scale<P>(dz_bound);
   const float inv_n = 1.f / ((float)N * (float)HW);
   constexpr bool zm = MASK == 2;
-  float cmu[8], crs[8], ca[8], k1[8], k2[8], cmb[8];
+  float cmu[8], crs[8], ca[8], k1[8], k2[8], cm0[8], cmb[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) {
     const int c = 8 * g + e;
     cmu[e] = mean[c];
     crs[e] = rstd[c];
     ca[e] = gamma[c] * crs[e];
-    cmb[e] = zm ? mbeta[c] - cmu[e] * ca[e] : 0.f;
+    cm0[e] = cmb[e] = 0.f;
+    if (zm) {  // the forward kernels' own map for the mask (bn_forward_map gives the same a = gamma rstd)
+      float fa;
+      bn_forward_map(gamma[c], mbeta[c], cmu[e], crs[e], fa, cm0[e], cmb[e]);
+    }
     k1[e] = train ? dbeta[c] * inv_n : 0.f;
     k2[e] = train ? dgamma[c] * inv_n : 0.f;
   }
@@ -845,7 +871,7 @@ __global__ __launch_bounds__(BN_V4_NT) void bn_bwd_apply_cb_v4_kernel(const floa
       } else if (zm) {
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (!(fmaf(zv[j], ca[e], cmb[e]) > 0.f)) gv[j] = 0.f;
+          if (!(fmaf(zv[j] - cm0[e], ca[e], cmb[e]) > 0.f)) gv[j] = 0.f;
       } else if (MASK == 1) {
         const float4 y4 = yq[e];
         const float yv[4] = {y4.x, y4.y, y4.z, y4.w};
@@ -1265,8 +1291,8 @@ extern "C" int mcdseg_bn_bwd_apply_cb(const float* dy, const float* y, const voi
   return 0;
 }
 
-// the same for a ReLU group WITHOUT residual, the mask recomputed from z (y > 0 <=> fma(z, gamma rstd, beta - mean gamma rstd) > 0, the
-// forward kernels' own expression): y is not read -- 12 instead of 16 bytes per element
+// the same for a ReLU group WITHOUT residual, the mask recomputed from z (y > 0 <=> the forward kernels' own map of z,
+// bn_forward_map, > 0): y is not read -- 12 instead of 16 bytes per element
 extern "C" int mcdseg_bn_bwd_apply_cb_zmask(const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
                                             const float* beta, const float* dgamma, const float* dbeta, float* dz, void* dz_cb,
                                             const float* dz_bound, int32_t math, int32_t N, int32_t C, int32_t HW, int32_t train,

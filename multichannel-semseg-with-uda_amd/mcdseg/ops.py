@@ -1145,7 +1145,7 @@ def _conv_backward(desc, x, dy, wd, need_dx, need_dw, dy_cb=None, x_cb=None, dy_
 MASK_NONE = "none"   # no ReLU
 MASK_Y = "y"         # the fp32 activation
 MASK_Y_CB = "y_cb"   # the sign of the leading piece of the activation's companion (compact storage, the 2-byte chain)
-MASK_Z = "z"         # recomputed from z: y > 0 <=> fma(z, gamma rstd, beta - mean gamma rstd) > 0 (BN_ZMASK; no residual enters)
+MASK_Z = "z"         # recomputed from z: y > 0 <=> the forward kernels' own map of z > 0 (csrc/bn.hip bn_forward_map; BN_ZMASK; no residual enters)
 MASK_BITS = "bits"   # the bit-plane the forward pass wrote (RELU_MASK; an fp32 residual)
 
 
