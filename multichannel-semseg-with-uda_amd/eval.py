@@ -13,7 +13,8 @@ from mcdseg import ops
 
 def fast_hist(a, b, n, out=None):
     """confusion matrix rows = ground truth ``a``, columns = prediction ``b``; entries with a outside [0,n) are dropped
-    (eval.py:21-23).  ``out`` (int64 [n,n] on the GPU) is accumulated into when given."""
+    (eval.py:21-23), and so are entries with b outside [0,n), which the reference's bincount would count in a neighbouring row.
+    ``out`` (int64 [n,n] on the GPU) is accumulated into when given."""
     if out is None:
         out = torch.zeros((n, n), dtype=torch.int64, device=a.device)
     return ops.confusion_hist_(out, a.reshape(-1), b.reshape(-1))

@@ -2241,7 +2241,9 @@ def relabel_u8(src, olabel, nlabel):
 
 
 def confusion_hist_(hist, gt, pred):
-    """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated."""
+    """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated.  An entry
+    whose prediction lies outside [0, n) is dropped too: it is not binned into a neighbouring row, as the reference's
+    bincount(n*gt + pred) would do."""
     gt, pred = _req(gt.long(), "ground truth", torch.int64), _req(pred.long(), "prediction", torch.int64)
     if gt.numel() != pred.numel():
         raise ValueError("mcdseg: confusion_hist_ needs as many predictions as labels")

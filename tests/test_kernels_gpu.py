@@ -2151,6 +2151,59 @@ def test_confusion_hist_full_size_checksum():
     assert torch.equal(hist.sum(0), torch.bincount(pred[keep], minlength=41))
 
 
+def _hist_statement(gt, pred, n):
+    """ops.confusion_hist_'s docstring in numpy: hist[gt, pred] += 1 where 0 <= gt < n and 0 <= pred < n, every other entry dropped"""
+    gt, pred = np.asarray(gt, dtype=np.int64).reshape(-1), np.asarray(pred, dtype=np.int64).reshape(-1)
+    keep = (gt >= 0) & (gt < n) & (pred >= 0) & (pred < n)
+    hist = np.zeros((n, n), dtype=np.int64)
+    np.add.at(hist, (gt[keep], pred[keep]), 1)
+    return hist
+
+
+@pytest.mark.parametrize("n", [1, 2, 41, 64, 65], ids=lambda n: "n%d" % n)
+@pytest.mark.parametrize("count", [1, 255, 4097], ids=lambda c: "count%d" % c)
+def test_confusion_hist_edges(count, n):
+    """fewer entries than one workgroup, one less than a workgroup, one more than a workgroup's 4096-entry share; one class, the largest
+    matrix kept in LDS bins (64: 16 KB) and the first in global bins (65); labels AND predictions outside [0, n) -- n itself, 255, -1 --
+    are dropped, not binned into a neighbouring row as bincount(n * gt + pred) would; a second call accumulates"""
+    dev = _dev()
+    import eval as mc_eval
+    rs = np.random.RandomState(100 * n + count % 97)
+    outside = np.array([n, 255, -1, n + 1, -n], dtype=np.int64)
+
+    def draw():
+        gt, pred = rs.randint(0, n, size=count).astype(np.int64), rs.randint(0, n, size=count).astype(np.int64)
+        for v in (gt, pred):
+            hit = rs.rand(count) < 0.25
+            v[hit] = outside[rs.randint(0, len(outside), size=int(hit.sum()))]
+        return gt, pred
+    gt, pred = draw()
+    if count >= 255:  # every kind of entry occurs, and each corner of the matrix is hit
+        gt[:8], pred[:8] = [n, 0, -1, n - 1, 255, 0, n - 1, 0], [0, n, n - 1, -1, 0, 255, n - 1, 0]
+        assert ((gt < 0) | (gt >= n)).sum() > 20 and ((pred < 0) | (pred >= n)).sum() > 20
+    else:
+        gt[0], pred[0] = 0, n  # the single entry is an out-of-range prediction on a valid label
+    ref = _hist_statement(gt, pred, n)
+    if count >= 255:
+        assert 0 < ref.sum() < count and ref[0, 0] > 0 and ref[n - 1, n - 1] > 0
+        # what the reference's bincount does with such predictions is NOT what is pinned: it moves them into a neighbouring row
+        k = (gt >= 0) & (gt < n) & (n * gt + pred >= 0)
+        assert n == 1 or not np.array_equal(np.bincount(n * gt[k] + pred[k], minlength=n * n)[:n * n].reshape(n, n), ref)
+    else:
+        assert ref.sum() == 0
+    hist = mc_eval.fast_hist(torch.from_numpy(gt).to(dev), torch.from_numpy(pred).to(dev), n)
+    assert hist.dtype == torch.int64 and tuple(hist.shape) == (n, n)
+    assert np.array_equal(hist.cpu().numpy(), ref)
+    gt2, pred2 = draw()
+    if count < 255:
+        gt2[0], pred2[0] = n - 1, 0  # a valid single entry
+    again = mc_eval.fast_hist(torch.from_numpy(gt2).to(dev), torch.from_numpy(pred2).to(dev), n, out=hist)
+    assert again is hist
+    assert np.array_equal(hist.cpu().numpy(), ref + _hist_statement(gt2, pred2, n))
+    if count < 255:
+        assert int(hist.sum()) == 1 and int(hist[n - 1, 0]) == 1
+
+
 def test_stem_direct_conv_matches_generic_kernels(monkeypatch):
     """the stem's direct convolution (bf16x6) against fp64 and against the f32-MFMA implicit GEMM: plain, with bias, and the
     folded-BN inference epilogue (scale, shift, ReLU)"""
