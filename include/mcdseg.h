@@ -465,6 +465,40 @@ int mcdseg_boundary_head_bce_fwd(const float* s1, const float* s2, const float* 
 int mcdseg_boundary_head_bce_bwd(const float* s1, const float* s2, const float* s3, const int64_t* labels, const float* beta,
                                  const float* upstream, float* ds1, float* ds2, float* ds3, int32_t N, int32_t H, int32_t W, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Boundary losses of the triple multitask decoder (MCDTripleMultiTaskDecoder, models/dilated_fcn.py:790-1024).  A target here is one
+ * plane [H,W] per image, fp32 (soft targets in [0,1] allowed) or uint8 {0,1} when target_u8 != 0; image n's plane starts
+ * n * target_batch_stride elements behind `target` (>= H*W: a channel of a wider batch is read in place).  Sums as above: fp64 block
+ * partials, one small kernel, no float atomics, bitwise reproducible; nothing synchronises with the host.
+ *   boundary_head_bce_target (get_boundary_loss, :1002-1004: bce2d(boundary_forward(x), gt_boundary)): mcdseg_boundary_head_bce with the
+ *     target given instead of derived from labels, built from the same device functions -- the gradients equal the composition
+ *     boundary_head -> bce2d bit for bit, the loss up to the order of its partial sums.  workspace: mcdseg_bce2d_workspace_bytes(N*H*W).
+ *   seg2bd_bce (get_boundary_loss_by_extra_conv, :960-981, with seg2bd_conv = nn.Conv2d(C, 1, 5, padding=2) of :863-864): per head,
+ *     u = bilinear8(z) (mcdseg_bilinear8_fwd's map, align_corners = False; 0 outside [0,H) x [0,W): the padding pads u, not z),
+ *     v[n,y,x] = b + sum_{c,i,j} w[c,i,j] u[n,c,y+i-2,x+j-2], q = 1 / (1 + expf(-v)), loss = bce2d(q, t) as mcdseg_bce2d defines it.
+ *     z1, z2 [N,C,Hi,Wi] are the two heads' low-resolution logits (z2 NULL: one head), H = 8 Hi, W = 8 Wi, w [1,C,5,5], b [1].
+ *     out[0], out[1] = the heads' losses (out[1] = 0 with one head), out[2] = beta.  Both maps being linear, the channel sum is taken
+ *     at LOW resolution (25 planes sum_c w[c,k] z[c] forward, 25 planes B^T(shifted dL/dv) backward): no C-channel full-resolution
+ *     tensor exists in either pass; the workspace holds v and dL/dv (one plane per head each), the 25 planes and the partials.
+ *     _bwd: bce2d_bwd -> sigmoid -> 5x5 transpose -> bilinear transpose with torch's clamp (-100) and eps (1e-12) as mcdseg_bce2d_bwd has
+ *     them; beta = out + 2 of the forward call, upstream [2] = the two losses' incoming gradients (NULL: 1, 1), both read on the
+ *     device; dz1, dz2 (NULL iff z2 is) in gather form, dw [1,C,5,5] and db [1] summed over both heads and all pixels in fp64.  _bwd
+ *     needs the workspace its _fwd call left (v); it changes nothing _fwd wrote, so it may be repeated.
+ * ---------------------------------------------------------------------------------------------- */
+int mcdseg_boundary_head_bce_target_fwd(const float* s1, const float* s2, const float* s3, const void* target, int32_t target_u8,
+                                        int64_t target_batch_stride, float* out, int32_t N, int32_t H, int32_t W, void* workspace,
+                                        size_t workspace_bytes, void* stream);
+int mcdseg_boundary_head_bce_target_bwd(const float* s1, const float* s2, const float* s3, const void* target, int32_t target_u8,
+                                        int64_t target_batch_stride, const float* beta, const float* upstream, float* ds1, float* ds2,
+                                        float* ds3, int32_t N, int32_t H, int32_t W, void* stream);
+size_t mcdseg_seg2bd_bce_workspace_bytes(int32_t N, int32_t C, int32_t Hi, int32_t Wi);
+int mcdseg_seg2bd_bce_fwd(const float* z1, const float* z2, const float* w, const float* b, const void* target, int32_t target_u8,
+                          int64_t target_batch_stride, float* out, int32_t N, int32_t C, int32_t Hi, int32_t Wi, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int mcdseg_seg2bd_bce_bwd(const float* z1, const float* z2, const float* w, const float* b, const void* target, int32_t target_u8,
+                          int64_t target_batch_stride, const float* beta, const float* upstream, float* dz1, float* dz2, float* dw,
+                          float* db, int32_t N, int32_t C, int32_t Hi, int32_t Wi, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Scale(img_shape, Image.BILINEAR) / Scale(img_shape, Image.NEAREST) in front of the two transforms below (transform.py:303,
  * 320; torchvision's Scale = PIL.Image.resize) on uint8 batches: src [N,H,W,C] -> dst [N,OH,OW,C] (bilinear; Pillow's 8-bit
  * ImagingResample, bit for bit) and src [N,H,W] -> dst [N,OH,OW] (nearest; ImagingScaleAffine, for label maps).  workspace: 4-byte

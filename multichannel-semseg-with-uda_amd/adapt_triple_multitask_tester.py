@@ -1,0 +1,92 @@
+#!/usr/bin/env python3
+"""Segmentation + depth + boundary multitask MCD inference -- the reference's ``adapt_triple_multitask_tester.py`` (:1-187): load an
+``adapt_triple_multitask_trainer`` checkpoint (``enc_state_dict`` / ``dec_state_dict``), run the stage-tap RGB encoder on
+``imgs[:, :3]`` and the decoder in eval mode, and write per image
+
+    label/<name>       argmax of pred_semseg1 over the non-background classes, resized NEAREST to the test shape
+    depth/<name>       the depth head as an RGB image (transform.unnormalize), resized BILINEAR to the test shape
+    boundary/<name>    np.uint8(pred_boundary * 255) (numpy's own cast, on the host), resized BILINEAR to the test shape
+    prob/<name>.npy    pred_semseg1 at full resolution (only with --saves_prob)
+
+plus ``ave_ent_<x>.txt`` (mean entropy of pred_semseg1) and, when the data carry ground truth, ``eval_result.json``.
+
+The segmentation and depth heads run at 1/8 resolution; the x8 bilinear up-sampling is fused into the argmax / entropy kernel
+(``mcdseg_predict_labels_up8``) and into the depth-image kernel (``mcdseg_depth_image_u8``); the boundary map is one pass of
+``mcdseg_boundary_head_fwd``.  pred_semseg2 is not evaluated: the reference computes it and drops it (its F2 average is commented out,
+:124-126), so ``--use_f2`` only renames the output directory, as there.  ``use_seg2bd_conv`` is back-filled to False for checkpoints
+written before the flag existed (:82-83).  The palette visualisation (``vis/``) and ``eval.py`` run of the reference are outside this
+build, as in the other testers.
+
+    python adapt_triple_multitask_tester.py nyu train_output/...MCD_triple_multitask/pth/MCD-normal-drn_d_38-40.pth.tar --synthetic
+"""
+import os
+
+import numpy as np
+import torch
+from PIL import Image
+
+import tester_common
+from argmyparse import add_additional_params_to_args, get_da_mcd_testing_parser
+from models.model_util import get_triple_multitask_models
+from trainer_common import criteria
+from util import mkdir_if_not_exist
+from mcdseg import ops
+
+
+def backfill(train_args):
+    if "use_seg2bd_conv" not in vars(train_args):
+        train_args.use_seg2bd_conv = False
+    return train_args
+
+
+def main(argv=None):
+    args = add_additional_params_to_args(get_da_mcd_testing_parser().parse_args(argv))
+    t = tester_common.start(args)
+    train_args = backfill(t.train_args)
+
+    # the criteria are not used here, but the decoder holds the class weights as a buffer (semseg_criterion.nll_loss.weight) and the
+    # checkpoint carries it, so they are built as the trainer built them (adapt_triple_multitask_tester.py:74-92)
+    criterion, criterion_d = criteria(train_args)
+    model_enc, model_dec = get_triple_multitask_models(
+        net_name=train_args.net, input_ch=train_args.input_ch, n_class=train_args.n_class,
+        is_data_parallel=getattr(train_args, "is_data_parallel", False), semseg_criterion=criterion, discrepancy_criterion=criterion_d,
+        semseg_shortcut=getattr(train_args, "semseg_shortcut", False), depth_shortcut=getattr(train_args, "depth_shortcut", False),
+        add_pred_seg_boundary_loss=getattr(train_args, "add_pred_seg_boundary_loss", False), use_seg2bd_conv=train_args.use_seg2bd_conv)
+    model_enc.load_state_dict(t.checkpoint["enc_state_dict"])
+    model_dec.load_state_dict(t.checkpoint["dec_state_dict"])
+    enc, dec = tester_common.unwrap(model_enc), tester_common.unwrap(model_dec)
+    print(dec.get_task_weights())
+    for m in (model_enc, model_dec):
+        m.eval()
+        m.to(t.dev)
+
+    outdirs = {name: os.path.join(t.base_outdir, name) for name in ("label", "depth", "boundary")}
+    for d in outdirs.values():
+        mkdir_if_not_exist(d)
+    total_ent, images = 0.0, 0
+    with torch.no_grad():
+        for imgs, gts, paths in t.loader:
+            imgs = imgs.to(t.dev, non_blocking=True)
+            feature = enc(imgs[:, :3, :, :].contiguous())
+            s1 = dec.semsegcls_dec1(feature["h8"])  # pred_semseg1 before the x8 up-sampling
+            dep = dec.deprgr_dec(feature["h8"])     # pred_depth before the x8 up-sampling
+            pred_boundary = dec.boundary_forward(feature)
+            labels, ent = ops.predict_labels_bilinear8(s1, t.n_used)
+            total_ent += float(ent) * len(paths)  # the reference's mean over images (it runs one image per batch)
+            images += len(paths)
+            tester_common.update_meter(t.meter, labels, gts, train_args.n_class)
+            if args.saves_prob:
+                tester_common.save_probs(t.base_outdir, paths, ops.bilinear8(s1))
+            lab = ops.resize_u8(labels, t.test_img_shape, nearest=True).cpu().numpy()
+            depth = ops.resize_u8(ops.depth_image_u8(dep), t.test_img_shape).cpu().numpy()
+            boundary = np.uint8(pred_boundary[:, 0].cpu().numpy() * 255)
+            for k, path in enumerate(paths):
+                name = os.path.basename(path)
+                Image.fromarray(lab[k]).save(os.path.join(outdirs["label"], name))
+                Image.fromarray(depth[k]).save(os.path.join(outdirs["depth"], name))
+                Image.fromarray(boundary[k]).resize(t.test_img_shape, Image.BILINEAR).save(os.path.join(outdirs["boundary"], name))
+    return outdirs, tester_common.finish(t.base_outdir, total_ent, images, t.meter)
+
+
+if __name__ == "__main__":
+    main()

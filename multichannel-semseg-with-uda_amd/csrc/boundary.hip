@@ -3,49 +3,18 @@
 //   boundary_head      p = (sigmoid(up2 s1) + sigmoid(up4 s2) + sigmoid(up8 s3)) / 3      (boundary_forward, :1118-1128)
 //   bce2d              class-balanced binary cross-entropy                                (loss.py:131-138)
 //   boundary_head_bce  the three of them in one forward and one backward pass             (get_boundary_loss, :1202-1204)
+//   boundary_head_bce_target  the same pair against a given target plane (MCDTripleMultiTaskDecoder.get_boundary_loss, :1002-1004)
 // HBM-bound streaming kernels on full-resolution maps.  Sums leave a block as fp64 partials and are finished by one small
 // kernel in fp64; no float atomics anywhere, so every result is bitwise reproducible.  The fused pair calls the very device
 // functions the unfused kernels are made of (fp contraction is off), which is what makes it equal to their composition.
 #include "common.h"
+#include "boundary_blocks.h"
 
 namespace {
 
 typedef long long ll2 __attribute__((ext_vector_type(2)));
 
 // ---------------------------------------------------------------------------------------------------------- building blocks
-// source index / weights of torch's upsample_bilinear2d (align_corners=False) at scale S: src = (dst + 0.5)/S - 0.5, clamped
-// at 0 (src_index of multitask.hip with 1/8 replaced by 1/S; S is a power of two, so 1/S is exact)
-template <int S>
-__device__ __forceinline__ void src_index_s(int dst, int in_size, int& i0, int& i1, float& l0, float& l1) {
-  float s = (1.f / (float)S) * ((float)dst + 0.5f) - 0.5f;
-  s = s < 0.f ? 0.f : s;
-  i0 = (int)s;
-  i1 = i0 + (i0 < in_size - 1 ? 1 : 0);
-  l1 = s - (float)i0;
-  l0 = 1.f - l1;
-}
-
-template <int S>
-__device__ __forceinline__ float tap_weight_s(int dst, int in_size, int i) {
-  int i0, i1;
-  float l0, l1;
-  src_index_s<S>(dst, in_size, i0, i1, l0, l1);
-  return (i0 == i ? l0 : 0.f) + (i1 == i ? l1 : 0.f);
-}
-
-// the bilinear xS value at output pixel (oy, ox) of one low-resolution plane [Hi, Wi]
-template <int S>
-__device__ __forceinline__ float up_at(const float* __restrict__ pl, int Hi, int Wi, int oy, int ox) {
-  int y0, y1, x0, x1;
-  float ly0, ly1, lx0, lx1;
-  src_index_s<S>(oy, Hi, y0, y1, ly0, ly1);
-  src_index_s<S>(ox, Wi, x0, x1, lx0, lx1);
-  const float* r0 = pl + y0 * Wi;
-  const float* r1 = pl + y1 * Wi;
-  return ly0 * (lx0 * r0[x0] + lx1 * r0[x1]) + ly1 * (lx0 * r1[x0] + lx1 * r1[x1]);
-}
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + expf(-x)); }
 
 // the three planes of one image and the full-resolution size (H, W multiples of 8)
 struct Head {
@@ -94,42 +63,6 @@ __device__ __forceinline__ float boundary_at(const T* __restrict__ lab, int H, i
   return mx != mn ? 1.f : 0.f;
 }
 
-// F.binary_cross_entropy of the installed torch: both logarithms clamped at -100 before they are multiplied
-__device__ __forceinline__ float bce_term(float p, float t) {
-  const float lp = fmaxf(logf(p), -100.f);
-  const float lq = fmaxf(log1pf(-p), -100.f);
-  return (t - 1.f) * lq - t * lp;
-}
-
-// ... and its backward under the class-balancing weight w = 1 - beta + (2 beta - 1) t; gs = upstream / n
-__device__ __forceinline__ float bce_grad(float p, float t, float beta, float gs) {
-  const float w = (1.f - beta) + (2.f * beta - 1.f) * t;
-  return gs * (p - t) / fmaxf((1.f - p) * p, 1e-12f) * w;
-}
-
-struct Sums {
-  float t, b, tb;
-};
-
-__device__ __forceinline__ void sums_add(Sums& s, float p, float t) {
-  const float b = bce_term(p, t);
-  s.t += t;
-  s.b += b;
-  s.tb += t * b;
-}
-
-// block partials: [block][3] doubles (sum t, sum bce, sum t*bce)
-__device__ __forceinline__ void sums_store(const Sums& s, double* __restrict__ part) {
-  __shared__ double sh[3][4];
-  const double a = wave_sum_d((double)s.t), b = wave_sum_d((double)s.b), c = wave_sum_d((double)s.tb);
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = a;
-    sh[1][threadIdx.x >> 6] = b;
-    sh[2][threadIdx.x >> 6] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) part[(size_t)blockIdx.x * 3 + threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
-}
 
 // out[0] = loss = ((1 - beta) sum bce + (2 beta - 1) sum t bce) / n,  out[1] = beta = 1 - sum t / n
 __global__ __launch_bounds__(256) void bce_finalize_kernel(const double* __restrict__ part, int nblk, double n, float* __restrict__ out) {
@@ -151,10 +84,6 @@ __global__ __launch_bounds__(256) void bce_finalize_kernel(const double* __restr
   }
 }
 
-int sum_blocks(int64_t n) {
-  const int64_t b = ceil_div64(n, 256 * 16);
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
 
 // ---------------------------------------------------------------------------------------------------------- label_boundary
 __device__ __forceinline__ void load8(const long long* p, long long v[8]) {
@@ -343,6 +272,68 @@ int launch_head_bwd(const float* s1, const float* s2, const float* s3, const flo
   return 0;
 }
 
+// The fused backward against a GIVEN target (one plane per image, fp32 or uint8, image n's plane tstride elements behind image
+// n - 1's): boundary_head_bwd_kernel<S, true> with the target read instead of derived from the labels' 3x3 window.
+template <int S, typename T>
+__global__ __launch_bounds__(256) void boundary_head_bwd_target_kernel(const float* __restrict__ s1, const float* __restrict__ s2,
+                                                                       const float* __restrict__ s3, const T* __restrict__ tgt, int64_t tstride,
+                                                                       const float* __restrict__ beta_p, const float* __restrict__ g_p, float inv_n,
+                                                                       float* __restrict__ ds, int H, int W) {
+  const int img = blockIdx.x;
+  const Head h = head_of(s1, s2, s3, img, H, W);
+  const int Hi = H / S, Wi = W / S;
+  const T* ti = tgt + (size_t)img * tstride;
+  const float beta = *beta_p;
+  const float gs = (g_p ? *g_p : 1.f) * inv_n;
+  const int total = Hi * Wi;
+  for (int idx = blockIdx.y * blockDim.x + threadIdx.x; idx < total; idx += gridDim.y * blockDim.x) {
+    const int iy = idx / Wi;
+    const int ix = idx - iy * Wi;
+    const int oy0 = S * iy - S / 2, ox0 = S * ix - S / 2;
+    float acc = 0.f;
+    for (int ky = 0; ky < 2 * S; ++ky) {
+      const int oy = oy0 + ky;
+      if (oy < 0 || oy >= H) continue;
+      const float wy = tap_weight_s<S>(oy, Hi, iy);
+      if (wy == 0.f) continue;  // (a clamped edge tap)
+      float r = 0.f;
+      for (int kx = 0; kx < 2 * S; ++kx) {
+        const int ox = ox0 + kx;
+        if (ox < 0 || ox >= W) continue;
+        const float wx = tap_weight_s<S>(ox, Wi, ix);
+        if (wx == 0.f) continue;
+        float g1, g2, g3;
+        head_sigmoids(h, oy, ox, g1, g2, g3);
+        const float sg = S == 2 ? g1 : (S == 4 ? g2 : g3);
+        const float d = bce_grad(head_mean(g1, g2, g3), (float)ti[(size_t)oy * W + ox], beta, gs);
+        r = fmaf((d / 3.f) * ((1.f - sg) * sg), wx, r);
+      }
+      acc = fmaf(wy, r, acc);
+    }
+    ds[(size_t)img * total + idx] = acc;
+  }
+}
+
+template <typename T>
+int launch_head_bwd_target(const float* s1, const float* s2, const float* s3, const T* tgt, int64_t tstride, const float* beta, const float* g,
+                           float* ds1, float* ds2, float* ds3, int N, int H, int W, hipStream_t st) {
+  const float inv_n = (float)(1.0 / ((double)N * H * W));
+  auto chunks = [](int px) {
+    const int c = ceil_div(px, 256);
+    return c > 256 ? 256 : c;
+  };
+  hipLaunchKernelGGL((boundary_head_bwd_target_kernel<2, T>), dim3(N, chunks((H / 2) * (W / 2))), dim3(256), 0, st, s1, s2, s3, tgt, tstride, beta, g,
+                     inv_n, ds1, H, W);
+  MCD_LAUNCH_CHECK("boundary_head_bwd_target<2>");
+  hipLaunchKernelGGL((boundary_head_bwd_target_kernel<4, T>), dim3(N, chunks((H / 4) * (W / 4))), dim3(256), 0, st, s1, s2, s3, tgt, tstride, beta, g,
+                     inv_n, ds2, H, W);
+  MCD_LAUNCH_CHECK("boundary_head_bwd_target<4>");
+  hipLaunchKernelGGL((boundary_head_bwd_target_kernel<8, T>), dim3(N, chunks((H / 8) * (W / 8))), dim3(256), 0, st, s1, s2, s3, tgt, tstride, beta, g,
+                     inv_n, ds3, H, W);
+  MCD_LAUNCH_CHECK("boundary_head_bwd_target<8>");
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------- bce2d
 __device__ __forceinline__ void load_t16(const uint8_t* t, int64_t i16, float v[16]) {
   const uint4 a = reinterpret_cast<const uint4*>(t)[i16];
@@ -445,6 +436,23 @@ __global__ __launch_bounds__(256) void boundary_head_bce_fwd_kernel(const float*
   sums_store(s, part);
 }
 
+// the fused forward against a given target: one pixel per thread (any alignment of the planes), p from the three maps, the three sums
+template <typename T>
+__global__ __launch_bounds__(256) void boundary_head_bce_target_fwd_kernel(const float* __restrict__ s1, const float* __restrict__ s2,
+                                                                           const float* __restrict__ s3, const T* __restrict__ tgt, int64_t tstride,
+                                                                           double* __restrict__ part, int H, int W, int64_t total) {
+  const int64_t HW = (int64_t)H * W;
+  Sums s = {0.f, 0.f, 0.f};
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int img = (int)(i / HW);
+    const int r = (int)(i - img * HW);
+    const int y = r / W;
+    const Head h = head_of(s1, s2, s3, img, H, W);
+    sums_add(s, head_p(h, y, r - y * W), (float)tgt[(size_t)img * tstride + r]);
+  }
+  sums_store(s, part);
+}
+
 bool head_args_ok(int N, int H, int W) { return N > 0 && H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && (int64_t)H * W < (1ll << 31); }
 
 }  // namespace
@@ -531,4 +539,41 @@ extern "C" int mcdseg_boundary_head_bce_bwd(const float* s1, const float* s2, co
   MCD_REQUIRE(s1 && s2 && s3 && labels && beta && ds1 && ds2 && ds3 && head_args_ok(N, H, W),
               "boundary_head_bce_bwd: bad arguments (H and W must be multiples of 8)");
   return launch_head_bwd<true>(s1, s2, s3, nullptr, (const long long*)labels, beta, upstream, ds1, ds2, ds3, N, H, W, (hipStream_t)stream);
+}
+
+extern "C" int mcdseg_boundary_head_bce_target_fwd(const float* s1, const float* s2, const float* s3, const void* target, int32_t target_u8,
+                                                   int64_t target_batch_stride, float* out, int32_t N, int32_t H, int32_t W, void* workspace,
+                                                   size_t workspace_bytes, void* stream) {
+  MCD_REQUIRE(s1 && s2 && s3 && target && out && workspace && head_args_ok(N, H, W),
+              "boundary_head_bce_target_fwd: bad arguments (H and W must be multiples of 8)");
+  MCD_REQUIRE(target_batch_stride >= (int64_t)H * W, "boundary_head_bce_target_fwd: the target's batch stride is smaller than a plane");
+  MCD_REQUIRE(target_u8 || (reinterpret_cast<uintptr_t>(target) & 3) == 0, "boundary_head_bce_target_fwd: an fp32 target must be 4-byte aligned");
+  const int64_t n = (int64_t)N * H * W;
+  const int nb = sum_blocks(n);
+  MCD_REQUIRE(workspace_bytes >= (size_t)nb * 3 * sizeof(double) && (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
+              "boundary_head_bce_target_fwd: workspace too small or not 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  if (target_u8)
+    hipLaunchKernelGGL(boundary_head_bce_target_fwd_kernel<uint8_t>, dim3(nb), dim3(256), 0, st, s1, s2, s3, (const uint8_t*)target,
+                       target_batch_stride, (double*)workspace, H, W, n);
+  else
+    hipLaunchKernelGGL(boundary_head_bce_target_fwd_kernel<float>, dim3(nb), dim3(256), 0, st, s1, s2, s3, (const float*)target, target_batch_stride,
+                       (double*)workspace, H, W, n);
+  MCD_LAUNCH_CHECK("boundary_head_bce_target_fwd");
+  hipLaunchKernelGGL(bce_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)workspace, nb, (double)n, out);
+  MCD_LAUNCH_CHECK("boundary_head_bce_target_finalize");
+  return 0;
+}
+
+extern "C" int mcdseg_boundary_head_bce_target_bwd(const float* s1, const float* s2, const float* s3, const void* target, int32_t target_u8,
+                                                   int64_t target_batch_stride, const float* beta, const float* upstream, float* ds1, float* ds2,
+                                                   float* ds3, int32_t N, int32_t H, int32_t W, void* stream) {
+  MCD_REQUIRE(s1 && s2 && s3 && target && beta && ds1 && ds2 && ds3 && head_args_ok(N, H, W),
+              "boundary_head_bce_target_bwd: bad arguments (H and W must be multiples of 8)");
+  MCD_REQUIRE(target_batch_stride >= (int64_t)H * W, "boundary_head_bce_target_bwd: the target's batch stride is smaller than a plane");
+  MCD_REQUIRE(target_u8 || (reinterpret_cast<uintptr_t>(target) & 3) == 0, "boundary_head_bce_target_bwd: an fp32 target must be 4-byte aligned");
+  if (target_u8)
+    return launch_head_bwd_target(s1, s2, s3, (const uint8_t*)target, target_batch_stride, beta, upstream, ds1, ds2, ds3, N, H, W,
+                                  (hipStream_t)stream);
+  return launch_head_bwd_target(s1, s2, s3, (const float*)target, target_batch_stride, beta, upstream, ds1, ds2, ds3, N, H, W, (hipStream_t)stream);
 }

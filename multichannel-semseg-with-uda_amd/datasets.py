@@ -39,12 +39,19 @@ class SyntheticRGBD(data.Dataset):
 
     ``raw=True`` yields what a loader holds BEFORE the reference's transforms: a uint8 [H,W,C] image (RGB then HHA
     bytes) and a uint8 label map whose background pixels carry ``background_id`` -- the trainer then runs
-    ToTensor/Normalize/ReLabel on the MI355X (``DeviceInputPipeline``)."""
+    ToTensor/Normalize/ReLabel on the MI355X (``DeviceInputPipeline``).
+
+    ``input_ch == 7`` is the triple multitask trainer's source (RGB, HHA, boundary): the draw is the same, then channel 6 is overwritten
+    with the 0/1 boundary of the sample's own label map (3x3 dilation != 3x3 erosion), the {0,1} plane the reference's loader yields there
+    (datasets.py:680-695).  There is no raw form of it."""
 
     def __init__(self, length, input_ch, img_shape_wh, n_class, seed, test=False, raw=False, background_id=255):
         self.length, self.ch, self.n_class, self.seed, self.test = length, input_ch, n_class, seed, test
         self.w, self.h = int(img_shape_wh[0]), int(img_shape_wh[1])
         self.raw, self.background_id = raw, background_id
+        if raw and input_ch == 7:
+            raise NotImplementedError("SyntheticRGBD: the 7-channel (RGB, HHA, boundary) sample has no raw uint8 form -- "
+                                      "DeviceInputPipeline has no boundary column")
 
     def __len__(self):
         return self.length
@@ -58,6 +65,10 @@ class SyntheticRGBD(data.Dataset):
         else:
             img = torch.randn(self.ch, self.h, self.w, generator=g)
             lbl = torch.randint(0, self.n_class, (self.h, self.w), generator=g, dtype=torch.int64)
+            if self.ch == 7:
+                v = lbl.float()[None, None]
+                pool = torch.nn.functional.max_pool2d
+                img[6] = (pool(v, kernel_size=3, stride=1, padding=1) != -pool(-v, kernel_size=3, stride=1, padding=1))[0, 0].float()
         if self.test:
             return img, lbl, "synthetic_%06d.png" % i
         return img, lbl

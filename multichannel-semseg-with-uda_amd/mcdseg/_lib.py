@@ -126,6 +126,11 @@ _SIGNATURES = {
     "mcdseg_bce2d_bwd": (c_int, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "mcdseg_boundary_head_bce_fwd": (c_int, [c_void_p] * 5 + [c_i32] * 3 + [c_void_p, c_size_t, c_void_p]),
     "mcdseg_boundary_head_bce_bwd": (c_int, [c_void_p] * 9 + [c_i32] * 3 + [c_void_p]),
+    "mcdseg_boundary_head_bce_target_fwd": (c_int, [c_void_p] * 4 + [c_i32, c_i64, c_void_p] + [c_i32] * 3 + [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_boundary_head_bce_target_bwd": (c_int, [c_void_p] * 4 + [c_i32, c_i64] + [c_void_p] * 5 + [c_i32] * 3 + [c_void_p]),
+    "mcdseg_seg2bd_bce_workspace_bytes": (c_size_t, [c_i32] * 4),
+    "mcdseg_seg2bd_bce_fwd": (c_int, [c_void_p] * 5 + [c_i32, c_i64, c_void_p] + [c_i32] * 4 + [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_seg2bd_bce_bwd": (c_int, [c_void_p] * 5 + [c_i32, c_i64] + [c_void_p] * 6 + [c_i32] * 4 + [c_void_p, c_size_t, c_void_p]),
     "mcdseg_normalize_u8": (c_int, [c_void_p] * 4 + [c_i32] * 6 + [c_void_p]),
     "mcdseg_resize_workspace_bytes": (c_size_t, [c_i32] * 6),
     "mcdseg_resize_bilinear_u8": (c_int, [c_void_p, c_void_p] + [c_i32] * 6 + [c_void_p, c_size_t, c_void_p]),
@@ -165,7 +170,7 @@ def sources():
 # backward under two ranks per device.  The compiler forms these instructions on its own from scalar fp32 source code, so the
 # files below are compiled with the packed-fp32 feature off, and ``packed_f32_opsel_sites`` (tests/test_cabi_and_host.py)
 # disassembles the built library to prove that no such instruction is left in ANY kernel.
-NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip"}
+NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip", "seg2bd.hip"}
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden"]
 NO_PK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # (the host pass ignores it with a warning)
 OBJ_DIR = os.path.join(CSRC, "build")

@@ -1900,6 +1900,111 @@ def boundary_head_bce(s1, s2, s3, labels):
     return _BoundaryHeadBCE.apply(s1, s2, s3, labels)
 
 
+# ------------------------------------------------------------------------------------------------ boundary branch (triple decoder)
+def _target_planes(t, n, h, w, name):
+    """(tensor, batch stride in elements) of a boundary target: n planes [h,w] given as [n,h,w] or [n,1,h,w], uint8 or fp32.  A channel
+    slice of a wider batch (planes contiguous, images a fixed distance apart) is read in place; any other non-contiguous layout is copied."""
+    if t is None or not t.is_cuda:
+        _req(t, name)
+    if t.dtype not in (torch.uint8, torch.float32):
+        raise TypeError("mcdseg: %s must be torch.uint8 or torch.float32, got %s" % (name, t.dtype))
+    if tuple(t.shape) not in ((n, h, w), (n, 1, h, w)):
+        raise ValueError("mcdseg: %s %s does not match the resolution %s" % (name, tuple(t.shape), (n, h, w)))
+    st = t.stride()
+    if st[-1] == 1 and st[-2] == w and (n == 1 or st[0] >= h * w):
+        return t, (st[0] if n > 1 else h * w)
+    return t.contiguous(), h * w
+
+
+class _BoundaryHeadBCETarget(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s1, s2, s3, target):
+        L = lib()
+        s1, s2, s3, n, h, w = _head_maps(s1, s2, s3)
+        target, ctx.tstride = _target_planes(target, n, h, w, "boundary target")
+        out = torch.empty(2, dtype=torch.float32, device=s1.device)
+        ws = _ws64(L.mcdseg_bce2d_workspace_bytes(n * h * w), s1.device)
+        check(L.mcdseg_boundary_head_bce_target_fwd(_p(s1), _p(s2), _p(s3), _p(target), int(target.dtype == torch.uint8), ctx.tstride, _p(out),
+                                                    n, h, w, _p(ws), ctypes.c_size_t(ws.numel() * 8), _stream()), "boundary_head_bce_target_fwd")
+        ctx.save_for_backward(s1, s2, s3, target, out)
+        ctx.dims = (n, h, w)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        s1, s2, s3, target, out = ctx.saved_tensors
+        g = _req(grad_out.reshape(1), "grad_output")
+        n, h, w = ctx.dims
+        d1, d2, d3 = torch.empty_like(s1), torch.empty_like(s2), torch.empty_like(s3)
+        check(lib().mcdseg_boundary_head_bce_target_bwd(_p(s1), _p(s2), _p(s3), _p(target), int(target.dtype == torch.uint8), ctx.tstride,
+                                                        _p(out[1:]), _p(g), _p(d1), _p(d2), _p(d3), n, h, w, _stream()),
+              "boundary_head_bce_target_bwd")
+        return d1, d2, d3, None
+
+
+def boundary_head_bce_target(s1, s2, s3, target):
+    """``bce2d(boundary_head(s1, s2, s3), target)`` without the full-resolution prediction, forward and backward
+    (MCDTripleMultiTaskDecoder.get_boundary_loss, models/dilated_fcn.py:1002-1004); target [N,1,H,W] or [N,H,W], uint8 or fp32, possibly
+    one channel of a wider batch"""
+    if target.requires_grad:
+        raise ValueError("mcdseg: boundary_head_bce_target does not compute the gradient w.r.t. its target")
+    return _BoundaryHeadBCETarget.apply(s1, s2, s3, target)
+
+
+class _Seg2bdBCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z1, z2, weight, bias, target):
+        L = lib()
+        z1, z2 = _req(z1, "seg2bd logits 1"), _req(z2, "seg2bd logits 2")
+        weight, bias = _req(weight, "seg2bd_conv weight"), _req(bias, "seg2bd_conv bias")
+        if z1.dim() != 4 or (z2 is not None and z2.shape != z1.shape):
+            raise ValueError("mcdseg: seg2bd_bce takes logits [N,C,h,w] of one shape, got %s and %s"
+                             % (tuple(z1.shape), None if z2 is None else tuple(z2.shape)))
+        n, c, hi, wi = z1.shape
+        if tuple(weight.shape) != (1, c, 5, 5) or bias.numel() != 1:
+            raise ValueError("mcdseg: seg2bd_bce takes the weight [1,%d,5,5] and bias [1] of nn.Conv2d(C, 1, 5, padding=2), got %s, %s"
+                             % (c, tuple(weight.shape), tuple(bias.shape)))
+        target, ctx.tstride = _target_planes(target, n, 8 * hi, 8 * wi, "seg2bd target")
+        nbytes = L.mcdseg_seg2bd_bce_workspace_bytes(n, c, hi, wi)
+        if nbytes == 0:
+            raise ValueError("mcdseg: seg2bd_bce cannot take logits of shape %s" % (tuple(z1.shape),))
+        ws = _ws64(nbytes, z1.device)
+        out = torch.empty(3, dtype=torch.float32, device=z1.device)
+        check(L.mcdseg_seg2bd_bce_fwd(_p(z1), _p(z2), _p(weight), _p(bias), _p(target), int(target.dtype == torch.uint8), ctx.tstride, _p(out),
+                                      n, c, hi, wi, _p(ws), ctypes.c_size_t(ws.numel() * 8), _stream()), "seg2bd_bce_fwd")
+        ctx.save_for_backward(z1, z2, weight, bias, target, out)
+        ctx.ws = ws  # (v of the forward pass: what the backward starts from)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out[1].clone(), out
+
+    @staticmethod
+    def backward(ctx, g1, g2, _):
+        z1, z2, weight, bias, target, out = ctx.saved_tensors
+        n, c, hi, wi = z1.shape
+        up = _req(torch.stack([g1.reshape(()), g2.reshape(())]), "grad_output")
+        dz1 = torch.empty_like(z1)
+        dz2 = None if z2 is None else torch.empty_like(z2)
+        dw, db = torch.empty_like(weight), torch.empty_like(bias)
+        ws = ctx.ws
+        check(lib().mcdseg_seg2bd_bce_bwd(_p(z1), _p(z2), _p(weight), _p(bias), _p(target), int(target.dtype == torch.uint8), ctx.tstride,
+                                          _p(out[2:]), _p(up), _p(dz1), _p(dz2), _p(dw), _p(db), n, c, hi, wi, _p(ws),
+                                          ctypes.c_size_t(ws.numel() * 8), _stream()), "seg2bd_bce_bwd")
+        return dz1, dz2, dw, db, None
+
+
+def seg2bd_bce(z1, z2, weight, bias, target, return_beta=False):
+    """``bce2d(sigmoid(conv2d(bilinear8(z), weight, bias, padding=2)), target)`` for the two heads' low-resolution logits z1, z2 [N,C,h,w]
+    (z2 None: one head, loss2 is None) -> (loss1, loss2), from the low-resolution logits in one pass each way: no [N,C,8h,8w] tensor
+    exists forward or backward (MCDTripleMultiTaskDecoder.get_boundary_loss_by_extra_conv, models/dilated_fcn.py:960-981).  Gradients go
+    to z1, z2, weight [1,C,5,5] and bias [1]; target [N,1,8h,8w] or [N,8h,8w], uint8 or fp32 (soft allowed), possibly one channel of a
+    wider batch, is never differentiated."""
+    if target.requires_grad:
+        raise ValueError("mcdseg: seg2bd_bce does not compute the gradient w.r.t. its target")
+    loss1, loss2, out = _Seg2bdBCE.apply(z1, z2, weight, bias, target)
+    res = (loss1, None if z2 is None else loss2)
+    return res + (out[2],) if return_beta else res
+
+
 # ------------------------------------------------------------------------------------------------ losses
 def label_weight_sum(labels, class_weight, n_class, ignore_index=-100):
     """device scalar sum_i w[labels_i]"""

@@ -8,6 +8,7 @@
   MultiTaskEncoder / MCDMultiTaskDecoder            :554-566, 661-739   segmentation + HHA regression (cfg4)
   MultiTaskEncoderReturningMultipleFeaturemaps / get_boundary_loss / MCDSegBDMultiTaskDecoder
                                       :569-629, 743-787, 1027-1222      segmentation + boundary ("segbd")
+  MCDTripleMultiTaskDecoder           :790-1024 segmentation + HHA regression + boundary ("triple"), with the seg2bd convolution
 
 State-dict keys follow the reference: ``base.<stage>...``, ``seg.{weight,bias}``,
 ``up.weight`` / ``up1.weight`` / ``up2.weight``.
@@ -422,3 +423,133 @@ class MCDSegBDMultiTaskDecoder(nn.Module):
         value is the boundary task's standard deviation"""
         import numpy as np
         return (np.sqrt(np.exp(2 * self.s_semsegcls.data.cpu().numpy())), np.sqrt(np.exp(2 * self.s_boundary.data.cpu().numpy())))
+
+
+# ------------------------------------------------------------------------------------------------ segmentation + depth + boundary ("triple")
+class MCDTripleMultiTaskDecoder(nn.Module):
+    """Two segmentation heads and an HHA-regression head on ``h8`` + the HED-style boundary head on ``h2``, ``h3``, ``h8``, three learned
+    log-variance task weights (models/dilated_fcn.py:790-1024).  ``nmlrgr_dec`` is built and never used, as in the reference.  With
+    ``use_seg2bd_conv`` a 5x5 convolution on the segmentation logits predicts the boundary as well (``get_boundary_loss_by_extra_conv``):
+    ``seg2bd_conv`` holds its parameters, the convolution itself runs inside ``ops.seg2bd_bce`` on the decoders' 1/8-resolution outputs.
+    ``semseg_shortcut`` and ``depth_shortcut`` (decoders on full-resolution 512-channel maps) are not built.
+
+    ``logits=`` of the loss methods takes the pair ``_semseg_logits`` returned for the same features, for a caller that needs the
+    segmentation decoders' outputs twice (the solver's step A); the default runs the decoders, as the reference does."""
+
+    def __init__(self, n_class, depth_ch, semseg_criterion=None, discrepancy_criterion=None, semseg_shortcut=False,
+                 depth_shortcut=False, add_pred_seg_boundary_loss=False, use_seg2bd_conv=False):
+        super().__init__()
+        if semseg_shortcut:
+            raise NotImplementedError("semseg_shortcut (segmentation decoders on full-resolution 512-channel maps) is not implemented")
+        if depth_shortcut:
+            raise NotImplementedError("depth_shortcut (a depth decoder on full-resolution 512-channel maps) is not implemented")
+        self.s_semsegcls = Parameter(torch.ones(1))
+        self.s_deprgr = Parameter(torch.ones(1))
+        self.s_boundary = Parameter(torch.ones(1))
+        self.semsegcls_dec1 = ThreeLayerDecoder(n_class)
+        self.semsegcls_dec2 = ThreeLayerDecoder(n_class)
+        self.deprgr_dec = ThreeLayerDecoder(depth_ch)
+        self.nmlrgr_dec = ThreeLayerDecoder(depth_ch)
+        self.semseg_criterion = semseg_criterion
+        self.discrepancy_criterion = discrepancy_criterion
+        self.upsample3 = _Bilinear8()
+        self.conv1 = Conv2d(32, 1, kernel_size=1, stride=1, padding=0)
+        self.conv2 = Conv2d(64, 1, kernel_size=1, stride=1, padding=0)
+        self.conv3 = Conv2d(512, 1, kernel_size=1, stride=1, padding=0)
+        self.semseg_shortcut = semseg_shortcut
+        self.depth_shortcut = depth_shortcut
+        self.add_pred_seg_boundary_loss = add_pred_seg_boundary_loss
+        if self.add_pred_seg_boundary_loss:
+            self.s_pred_seg_boundary = Parameter(torch.ones(1))
+        self.use_seg2bd_conv = use_seg2bd_conv
+        if self.use_seg2bd_conv:
+            self.seg2bd_conv = nn.Conv2d(n_class, 1, kernel_size=5, padding=2)  # (parameters only: ops.seg2bd_bce applies them)
+
+    def _semseg_logits(self, x_dic):
+        """the two segmentation decoders' outputs at 1/8 resolution"""
+        return self.semsegcls_dec1(x_dic["h8"]), self.semsegcls_dec2(x_dic["h8"])
+
+    def semseg_forward(self, x_dic, logits=None):
+        z1, z2 = self._semseg_logits(x_dic) if logits is None else logits
+        return self.upsample3(z1), self.upsample3(z2)
+
+    def depth_forward(self, x_dic):
+        return self.upsample3(self.deprgr_dec(x_dic["h8"]))
+
+    def _boundary_maps(self, x_dic):
+        return self.conv1(x_dic["h2"]), self.conv2(x_dic["h3"]), self.conv3(x_dic["h8"])
+
+    def boundary_forward(self, x_dic):
+        return ops.boundary_head(*self._boundary_maps(x_dic))
+
+    def forward(self, x_dic):
+        pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic)
+        return pred_semseg1, pred_semseg2, self.depth_forward(x_dic), self.boundary_forward(x_dic)
+
+    def get_cls_descrepancy(self, x_dic):
+        pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic)
+        return self.discrepancy_criterion(pred_semseg1, pred_semseg2)
+
+    def get_semseg_loss(self, x_dic, gt_semseg, separately_returning=False, logits=None):
+        pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic, logits)
+        loss1 = self.semseg_criterion(pred_semseg1, gt_semseg)
+        loss2 = self.semseg_criterion(pred_semseg2, gt_semseg)
+        if self.add_pred_seg_boundary_loss:
+            # :941-949: the arg-max boundary of each head against the labels' -- values without a gradient (the reference's ``.cuda()``
+            # on them only moves a value to the device)
+            argmax = MCDSegBDMultiTaskDecoder._argmax_labels
+            loss1 = loss1 + get_boundary_loss(argmax(pred_semseg1), gt_semseg)
+            loss2 = loss2 + get_boundary_loss(argmax(pred_semseg2), gt_semseg)
+        return (loss1, loss2) if separately_returning else loss1 + loss2
+
+    def get_depth_loss(self, x_dic, gt_dep):
+        return ops.mse_loss(self.depth_forward(x_dic), gt_dep)
+
+    def get_boundary_loss_by_extra_conv(self, x_dic, gt_bdry=None, separately_returning=False, logits=None):
+        """:960-981: bce2d(sigmoid(seg2bd_conv(pred_semseg)), target) per head, from the 1/8-resolution logits in one fused pass each
+        way; ``gt_bdry`` None takes the detached ``boundary_forward`` as a soft target."""
+        assert self.use_seg2bd_conv
+        z1, z2 = self._semseg_logits(x_dic) if logits is None else logits
+        if gt_bdry is None:
+            with torch.no_grad():  # "do not compute gradients w.r.t target"
+                gt_bdry = self.boundary_forward(x_dic)
+        elif gt_bdry.dtype not in (torch.float32, torch.uint8):
+            gt_bdry = gt_bdry.float()
+        loss1, loss2 = ops.seg2bd_bce(z1, z2, self.seg2bd_conv.weight, self.seg2bd_conv.bias, gt_bdry.detach())
+        return (loss1, loss2) if separately_returning else loss1 + loss2
+
+    def get_psuedo_boundary_loss(self, x_dic, separately_returning=False):
+        """:983-1000.  The reference raises TypeError here: it passes ``pred_semseg=`` to ``get_boundary_loss``, whose parameter is
+        ``pred``.  Built as MCDSegBDMultiTaskDecoder's (:1183-1200), which is what the call was copied from: each head's arg-max boundary
+        against the detached boundary head -- a value without a gradient, computed without a tape."""
+        assert self.add_pred_seg_boundary_loss
+        with torch.no_grad():
+            psuedo_boundary = self.boundary_forward(x_dic)
+            pred_semseg1, pred_semseg2 = self.semseg_forward(x_dic)
+            argmax = MCDSegBDMultiTaskDecoder._argmax_labels
+            loss1 = get_boundary_loss(pred=argmax(pred_semseg1), gt=psuedo_boundary, gt_type="boundary")
+            loss2 = get_boundary_loss(pred=argmax(pred_semseg2), gt=psuedo_boundary, gt_type="boundary")
+        return (loss1, loss2) if separately_returning else loss1 + loss2
+
+    def get_boundary_loss(self, x_dic, gt_boundary):
+        """:1002-1004: bce2d(boundary_forward(x), gt_boundary), the head and the loss in one pass each way"""
+        if gt_boundary.dtype not in (torch.float32, torch.uint8):
+            gt_boundary = gt_boundary.float()
+        return ops.boundary_head_bce_target(*self._boundary_maps(x_dic), gt_boundary.detach())
+
+    def _semseg_task_loss(self, x, gt_semseg, logits=None):
+        loss1, loss2 = self.get_semseg_loss(x, gt_semseg, separately_returning=True, logits=logits)
+        s = self.s_semsegcls
+        return ((torch.exp(-s) * loss1 + s) + (torch.exp(-s) * loss2 + s)) / 2
+
+    def get_loss(self, x, gt_semseg, gt_dep, gt_boundary, separately_returning=False, logits=None):
+        semseg_loss = self._semseg_task_loss(x, gt_semseg, logits)
+        depreg_loss = torch.exp(-self.s_deprgr) * self.get_depth_loss(x, gt_dep) + self.s_deprgr
+        boundary_loss = torch.exp(-self.s_boundary) * self.get_boundary_loss(x, gt_boundary) + self.s_boundary
+        if separately_returning:
+            return semseg_loss, depreg_loss, boundary_loss
+        return semseg_loss + depreg_loss + boundary_loss
+
+    def get_task_weights(self):
+        import numpy as np
+        return (np.sqrt(np.exp(2 * self.s_semsegcls.data.cpu().numpy())), np.sqrt(np.exp(2 * self.s_deprgr.data.cpu().numpy())))

@@ -106,6 +106,26 @@ def get_segbd_multitask_models(net_name, input_ch, n_class, semseg_criterion=Non
     return model_enc, model_dec
 
 
+def get_triple_multitask_models(net_name, input_ch, n_class, semseg_criterion=None, discrepancy_criterion=None,
+                                is_data_parallel=False, semseg_shortcut=False, depth_shortcut=False,
+                                add_pred_seg_boundary_loss=False, is_src_only=False, use_seg2bd_conv=False):
+    """Stage-tap RGB encoder + segmentation / depth / boundary decoder (models/model_util.py:102-130).  ``input_ch`` is ignored as in
+    the reference: the encoder always takes the 3 RGB channels and the depth head always regresses 3 (HHA) channels."""
+    if "drn" not in net_name:
+        raise NotImplementedError("Only FCN (Including Dilated FCN), SegNet, PSPNet UNet are supported!")
+    if is_src_only:
+        raise NotImplementedError("the source-only triple decoder (TripleMultiTaskDecoder) is outside the MCD hot path")
+    from models.dilated_fcn import MCDTripleMultiTaskDecoder, MultiTaskEncoderReturningMultipleFeaturemaps
+    model_enc = MultiTaskEncoderReturningMultipleFeaturemaps(model_name=net_name, input_ch=3, pretrained=_pretrained_default())
+    model_dec = MCDTripleMultiTaskDecoder(n_class=n_class, depth_ch=3, semseg_criterion=semseg_criterion,
+                                          discrepancy_criterion=discrepancy_criterion, semseg_shortcut=semseg_shortcut,
+                                          depth_shortcut=depth_shortcut, add_pred_seg_boundary_loss=add_pred_seg_boundary_loss,
+                                          use_seg2bd_conv=use_seg2bd_conv)
+    if is_data_parallel:
+        return _wrap(model_enc, True), _wrap(model_dec, True)
+    return model_enc, model_dec
+
+
 def get_optimizer(model_parameters, opt, lr, momentum, weight_decay):
     params = [p for p in model_parameters if p.requires_grad]
     if opt == "sgd":

@@ -432,3 +432,102 @@ class SegBDMultiTaskMCDSolver:
             del tgt_fet
             self.opt_enc.step()
         return c_loss, loss.detach() / self.num_k, parts
+
+
+class TripleMultiTaskMCDSolver:
+    """Three-step update of the segmentation + depth + boundary multitask variant (two segmentation decoders, an HHA-regression decoder
+    and a boundary head on a stage-tap RGB encoder; the source batch carries RGB, HHA and a {0,1} boundary plane), statement for
+    statement after ``adapt_triple_multitask_trainer.py:187-290``:
+
+      A  enc, dec <- min  semseg(src) + depth(src) + depth(tgt) + boundary(src) [+ seg2bd(src), under use_seg2bd_conv]
+                          [+ scale_bd_loss * target term, once epoch > boundary_loss_converging_epoch]
+      B  dec      <- min  semseg(src) - discrepancy(tgt)
+      C  enc      <- min  discrepancy(tgt) * num_multiply_d_loss          (num_k times)
+
+    The target term is the pseudo-boundary loss under add_pred_seg_boundary_loss and the seg2bd loss against the detached boundary head
+    under use_seg2bd_conv; with both flags the second overwrites the first in the loss while the logged sum takes both (:222-234).  The
+    tape runs on BOTH encoder passes of step A: the target's depth loss reaches the encoder.
+
+    Elisions, each of which provably changes no result:
+      * step A takes ONE pass of the segmentation decoders for the logits that the cross-entropy and the seg2bd loss both consume
+        (the reference's second ``semseg_forward(src_fet)`` sees the same input under the same weights), under
+        ``ops.bn_running_updates(2)``, so their BatchNorm running statistics move twice as there;
+      * step B runs the encoder without a tape (only the decoder's optimizer steps there, and step C zeroes the encoder's gradients
+        first), and of ``get_loss`` it builds the segmentation part alone: the depth decoder still runs -- its running statistics move --
+        but without a graph, and the boundary head, which has no statistics and whose loss is dropped, does not run.
+    Every other forward of the reference runs, so every BatchNorm running statistic moves as it does there."""
+
+    def __init__(self, model_enc, model_dec, optimizer_enc, optimizer_dec, num_k=4, num_multiply_d_loss=1,
+                 add_pred_seg_boundary_loss=False, use_seg2bd_conv=False, boundary_loss_converging_epoch=5, scale_bd_loss=1):
+        self.enc, self.dec = model_enc, model_dec
+        self.opt_enc, self.opt_dec = optimizer_enc, optimizer_dec
+        self.num_k, self.mult = num_k, num_multiply_d_loss
+        self.add_pred_seg_boundary_loss = add_pred_seg_boundary_loss
+        self.use_seg2bd_conv = use_seg2bd_conv
+        self.boundary_loss_converging_epoch = boundary_loss_converging_epoch
+        self.scale_bd_loss = scale_bd_loss
+
+    def step(self, src_imgs, src_gt_semseg, tgt_imgs, epoch=0):
+        """returns (c_loss, d_loss, parts): parts = step A's (src_semseg_loss, src_depth_loss, tgt_depth_loss, src_boundary_loss,
+        what the epoch's tgt_psuedo_boundary_loss sum takes, src_extra_boundary_loss) -- the values the trainer logs"""
+        enc, dec = self.enc, self.dec
+        src_rgbs, tgt_rgbs = src_imgs[:, :3, :, :], tgt_imgs[:, :3, :, :]
+        src_depths, tgt_depths = src_imgs[:, 3:-1, :, :].contiguous(), tgt_imgs[:, 3:, :, :].contiguous()
+        src_boundary = src_imgs[:, -1:, :, :]  # (a view: the kernels read the plane in place)
+
+        # ---- A: encoder and decoder on source and target
+        self.opt_enc.zero_grad()
+        self.opt_dec.zero_grad()
+        src_fet = enc(src_rgbs)
+        tgt_fet = enc(tgt_rgbs)
+        logits = None
+        if self.use_seg2bd_conv:
+            with ops.bn_running_updates(2):  # get_loss's semseg_forward and get_boundary_loss_by_extra_conv's
+                logits = dec._semseg_logits(src_fet)
+        src_semseg_loss, src_depth_loss, src_boundary_loss = dec.get_loss(src_fet, src_gt_semseg, src_depths, src_boundary,
+                                                                          separately_returning=True, logits=logits)
+        tgt_depth_loss = dec.get_depth_loss(tgt_fet, tgt_depths)
+        src_extra_boundary_loss = 0
+        if self.use_seg2bd_conv:
+            src_extra_boundary_loss = dec.get_boundary_loss_by_extra_conv(src_fet, src_boundary, logits=logits)
+        tgt_psuedo_boundary_loss, tgt_logged = 0, 0
+        if epoch > self.boundary_loss_converging_epoch:
+            if self.add_pred_seg_boundary_loss:
+                tgt_psuedo_boundary_loss = dec.get_psuedo_boundary_loss(tgt_fet, separately_returning=False) * self.scale_bd_loss
+                tgt_logged = tgt_logged + tgt_psuedo_boundary_loss.detach()
+            if self.use_seg2bd_conv:
+                tgt_psuedo_boundary_loss = dec.get_boundary_loss_by_extra_conv(tgt_fet, separately_returning=False) * self.scale_bd_loss
+                tgt_logged = tgt_logged + tgt_psuedo_boundary_loss.detach()
+        loss = src_semseg_loss + src_depth_loss + tgt_depth_loss + src_boundary_loss + tgt_psuedo_boundary_loss + src_extra_boundary_loss
+        loss.backward()
+        c_loss = loss.detach()
+        parts = (src_semseg_loss.detach(), src_depth_loss.detach(), tgt_depth_loss.detach(), src_boundary_loss.detach(), tgt_logged,
+                 src_extra_boundary_loss.detach() if torch.is_tensor(src_extra_boundary_loss) else src_extra_boundary_loss)
+        del src_fet, tgt_fet, logits, loss
+        self.opt_enc.step()
+        self.opt_dec.step()
+
+        # ---- B: decoder only
+        self.opt_enc.zero_grad()
+        self.opt_dec.zero_grad()
+        with torch.no_grad():
+            src_fet = enc(src_rgbs)
+        src_semseg_loss = dec._semseg_task_loss(src_fet, src_gt_semseg)
+        with torch.no_grad():
+            dec.depth_forward(src_fet)  # (get_loss's depth part: its value is dropped, its BatchNorm statistics are not)
+            tgt_fet = enc(tgt_rgbs)
+        tgt_discrepancy = dec.get_cls_descrepancy(tgt_fet)
+        loss = src_semseg_loss - tgt_discrepancy
+        loss.backward()
+        del src_fet, tgt_fet
+        self.opt_dec.step()
+
+        # ---- C: encoder only, num_k times
+        for _ in range(self.num_k):
+            self.opt_enc.zero_grad()
+            tgt_fet = enc(tgt_rgbs)
+            loss = dec.get_cls_descrepancy(tgt_fet) * self.mult
+            loss.backward()
+            del tgt_fet
+            self.opt_enc.step()
+        return c_loss, loss.detach() / self.num_k, parts

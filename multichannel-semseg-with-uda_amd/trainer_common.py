@@ -106,14 +106,16 @@ def synthetic_spec(args, seed_offset, rank):
                 raw=getattr(args, "synthetic_raw", False), background_id=getattr(args, "background_id", 255))
 
 
-def make_loader(args, run, names_splits):
-    """DataLoader over one dataset or a ConcatDataset of (source, target); per-rank shard by seed."""
+def make_loader(args, run, names_splits, src_input_ch=None):
+    """DataLoader over one dataset or a ConcatDataset of (source, target); per-rank shard by seed.  ``src_input_ch``: the channel count
+    of the first (source) dataset where it is not ``args.input_ch`` (``Trainer.src_input_ch``)."""
     sets = []
     lists = [getattr(args, "src_file_list", None), getattr(args, "tgt_file_list", None)]
     for i, (name, split) in enumerate(names_splits):
         spec = synthetic_spec(args, 7 * i, run.rank) if (args.synthetic or getattr(args, "synthetic_raw", False)) else None
         sets.append(get_dataset(dataset_name=name, split=split, img_transform=None, label_transform=None, test=False,
-                                input_ch=args.input_ch, synthetic=spec, file_list=lists[i] if i < 2 else None))
+                                input_ch=src_input_ch if (i == 0 and src_input_ch is not None) else args.input_ch, synthetic=spec,
+                                file_list=lists[i] if i < 2 else None))
     ds = sets[0] if len(sets) == 1 else ConcatDataset(*sets)
     return torch.utils.data.DataLoader(ds, batch_size=args.batch_size, shuffle=True, pin_memory=True, drop_last=True)
 
@@ -131,6 +133,7 @@ class Trainer:
     backfill: tuple = ()                  # keys a resumed namespace may lack, beyond BACKFILL
     on_resume: typing.Callable = None     # (pickled args, command-line args): what the command line still decides on resume
     announces_resume: bool = False        # the two "=> load..." lines of adapt_trainer.py
+    src_input_ch: int = None              # channels of the source batch where they are not --input_ch (None: --input_ch, as for the target)
 
 
 Layout = collections.namedtuple("Layout", "pth_dir tflog_dir json_fn model_name")
@@ -234,7 +237,7 @@ def train(trainer, args):
 
     adapt = "tgt_dataset" in vars(args)  # (source, target) pairs and the per-iteration line, or one dataset
     train_loader = make_loader(args, run, [(args.src_dataset, args.src_split), (args.tgt_dataset, args.tgt_split)] if adapt
-                               else [(args.src_dataset, args.split)])
+                               else [(args.src_dataset, args.split)], src_input_ch=trainer.src_input_ch)
     for m in modules.values():
         m.to(run.device)
     run.sync_replicas(list(modules.values()))
