@@ -522,6 +522,29 @@ int mcdseg_normalize_u8(const uint8_t* src, float* dst, const float* mean, const
 int mcdseg_relabel_u8(const uint8_t* src, int64_t* dst, int64_t count, int32_t olabel, int32_t nlabel, void* stream);
 int mcdseg_confusion_hist(const int64_t* gt, const int64_t* pred, int64_t count, int32_t n, int64_t* hist, void* stream);
 
+/* The joint transform of the trainers (joint_transforms.py:248-255, wired in at adapt_trainer.py:101-102 / source_trainer.py:82-83):
+ * RandomHorizontallyFlip, RandomRotate(angle), RandomCrop(size) on an image and its label map together, as ONE gather from the
+ * output pixel back to the loader's bytes, equal to Pillow's result byte for byte.  Per-sample parameters (drawn on the host) are two
+ * device tables: affine [N][6] doubles = the matrix PIL.Image.rotate computes, and geom [N][10] int32 = {mode, flip, x1, y1,
+ * fa0..fa5}: mode 0 copy, 1 affine, 2 / 3 / 4 Pillow's ROTATE_180 / ROTATE_90 / ROTATE_270 fast paths; (x1, y1) the crop corner;
+ * fa* the 16.16 fixed-point matrix of Pillow's nearest path (affine_fixed).  A source position outside the image is 0.
+ *   joint_augment_u8:           img.transpose(FLIP_LEFT_RIGHT).rotate(a, BILINEAR).crop(...) (joint_transforms.py:65, 137, 43):
+ *                               src uint8 [N,H,W,Cs] -> dst uint8 [N,OH,OW,Cs]
+ *   joint_augment_normalize_u8: the same followed by ToTensor() + Normalize (transform.py:302-315, use_crop: no Scale), i.e. by
+ *                               normalize_u8: -> fp32 channels [c_off, c_off+Cs) of dst [N,C,OH,OW]; a fill pixel is byte 0 normalised
+ *   joint_augment_label_u8:     mask.transpose(FLIP_LEFT_RIGHT).rotate(a, NEAREST).crop(...): src uint8 [N,H,W] -> dst uint8 [N,OH,OW];
+ *                               the fill is label 0 (a real class), as in the reference.  H, W < 32768 (Pillow's fixed-point range).
+ *   joint_augment_relabel_u8:   the same followed by ToLabel() + ReLabel (transform.py:319-325), i.e. by relabel_u8: -> int64 */
+int mcdseg_joint_augment_u8(const uint8_t* src, uint8_t* dst, const double* affine, const int32_t* geom, int32_t N, int32_t H, int32_t W,
+                            int32_t Cs, int32_t OH, int32_t OW, void* stream);
+int mcdseg_joint_augment_normalize_u8(const uint8_t* src, float* dst, const float* mean, const float* std, const double* affine,
+                                      const int32_t* geom, int32_t N, int32_t H, int32_t W, int32_t Cs, int32_t OH, int32_t OW, int32_t C,
+                                      int32_t c_off, void* stream);
+int mcdseg_joint_augment_label_u8(const uint8_t* src, uint8_t* dst, const int32_t* geom, int32_t N, int32_t H, int32_t W, int32_t OH,
+                                  int32_t OW, void* stream);
+int mcdseg_joint_augment_relabel_u8(const uint8_t* src, int64_t* dst, const int32_t* geom, int32_t N, int32_t H, int32_t W, int32_t OH,
+                                    int32_t OW, int32_t olabel, int32_t nlabel, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2-byte activation storage (round 6): BASELINE config 5 ("drn_d_105 ... bf16 ... HBM-bound stress"; the network is the reference's
  * Bottleneck trunk, models/drn.py:62-100, 344-348, trained by adapt_trainer.py:155-220).  In the one-term arithmetic MCDSEG_MATH_F16X1

@@ -134,12 +134,24 @@ class DeviceInputPipeline(object):
     """``get_img_transform`` / ``get_lbl_transform`` (transform.py:302-325) on the GPU: pinned uint8 batches go over PCIe as
     bytes (4x fewer than fp32); ``Scale`` (bilinear for images, nearest for label maps: Pillow's 8-bit arithmetic, bit for bit),
     ToTensor+Normalize (HWC->NCHW) and ToLabel+ReLabel(background_id -> n_class-1) each are one kernel.  ``img_shape`` = (W, H)
-    as the reference passes it to ``Scale``; None leaves the size alone (the loader already produced it)."""
+    as the reference passes it to ``Scale``; None leaves the size alone (the loader already produced it).
 
-    def __init__(self, input_ch, n_class, device, normalize_way="imagenet", background_id=255, img_shape=None):
-        from mcdseg import ops
+    ``crop_size > 0`` puts ``get_joint_transform(crop_size, rotate_angle)`` (joint_transforms.py:248-255: random flip, rotation, crop of
+    image and label map together) in front, and -- ``use_crop`` of transform.py:302-325 -- drops ``Scale``.  The draw happens on the
+    host (``mcdseg.augment.JointTransform``, seeded with ``seed``); flip, rotation, crop and the ToTensor+Normalize / ToLabel+ReLabel
+    behind them are ONE gather kernel per tensor, whose bytes equal Pillow's.  One draw serves every image part and the label map of a
+    sample (``joint``); ``images`` / ``labels`` called on their own draw afresh (a target batch: the reference transforms the source
+    and the target dataset independently).  The rotation fills label maps with class 0, as the reference's ``mask.rotate`` does -- a
+    real class, not the background id.  ``crop_size <= 0``: no joint transform at all, also with ``rotate_angle`` set."""
+
+    def __init__(self, input_ch, n_class, device, normalize_way="imagenet", background_id=255, img_shape=None, crop_size=-1,
+                 rotate_angle=0, seed=None):
+        from mcdseg import augment, ops
         self._ops = ops
         self.input_ch, self.n_class, self.device, self.background_id = input_ch, n_class, device, background_id
+        self.joint_transform = augment.get_joint_transform(crop_size, rotate_angle, seed)
+        if self.joint_transform is not None:
+            img_shape = None  # use_crop: no Scale
         self.img_shape = None if img_shape is None else (int(img_shape[0]), int(img_shape[1]))
         if normalize_way == "imagenet":
             mean, std = IMAGENET_MEAN[:input_ch], IMAGENET_STD[:input_ch]
@@ -150,9 +162,35 @@ class DeviceInputPipeline(object):
         self.mean = torch.tensor(mean, dtype=torch.float32, device=device)
         self.std = torch.tensor(std, dtype=torch.float32, device=device)
 
-    def images(self, *parts):
-        """one or more uint8 [N,H,W,c_i] tensors (e.g. RGB and HHA) -> fp32 [N, sum c_i, H, W]"""
+    def draw(self, n, h, w):
+        """the joint transform's parameter tables for a batch of n samples of h x w pixels (None without a joint transform)"""
+        return None if self.joint_transform is None else self.joint_transform.draw(n, h, w)
+
+    def joint(self, parts, lbl_u8):
+        """image parts and label map of ONE batch under one draw per sample -> (fp32 images, int64 labels)"""
+        parts = parts if isinstance(parts, (list, tuple)) else [parts]
+        params = self.draw(*lbl_u8.shape[:3])
+        return self.images(*parts, params=params), self.labels(lbl_u8, params=params)
+
+    def images(self, *parts, params=None):
+        """one or more uint8 [N,H,W,c_i] tensors (e.g. RGB and HHA) -> fp32 [N, sum c_i, H, W] ([N, sum c_i, crop, crop] under
+        the joint transform; ``params``: the draw to use, default a fresh one)"""
         parts = [p.to(self.device, non_blocking=True) for p in parts]
+        if self.joint_transform is not None:
+            params = params if params is not None else self.draw(*parts[0].shape[:3])
+            n, c = parts[0].shape[0], sum(p.shape[3] for p in parts)
+            oh, ow = params.out_hw if params.resize_to is None else (params.resize_to[1], params.resize_to[0])
+            out = torch.empty((n, c, oh, ow), dtype=torch.float32, device=self.device)
+            off = 0
+            for p in parts:
+                mean, std = self.mean[off:off + p.shape[3]], self.std[off:off + p.shape[3]]
+                if params.resize_to is None:
+                    self._ops.joint_augment_normalize_u8_(out, p, params, mean, std, c_off=off)
+                else:  # the image is smaller than the crop: RandomCrop resizes (joint_transforms.py:38-39)
+                    u8 = self._ops.resize_u8(self._ops.joint_augment_u8(p, params, params.out_hw), params.resize_to)
+                    self._ops.normalize_u8_(out, u8, mean, std, c_off=off)
+                off += p.shape[3]
+            return out
         if self.img_shape is not None:
             parts = [self._ops.resize_u8(p, self.img_shape) for p in parts]
         n, h, w = parts[0].shape[:3]
@@ -164,8 +202,14 @@ class DeviceInputPipeline(object):
             off += p.shape[3]
         return out
 
-    def labels(self, lbl_u8):
+    def labels(self, lbl_u8, params=None):
         lbl_u8 = lbl_u8.to(self.device, non_blocking=True)
+        if self.joint_transform is not None:
+            params = params if params is not None else self.draw(*lbl_u8.shape[:3])
+            if params.resize_to is None:
+                return self._ops.joint_augment_relabel_u8(lbl_u8, params, params.out_hw, self.background_id, self.n_class - 1)
+            u8 = self._ops.resize_u8(self._ops.joint_augment_u8(lbl_u8, params, params.out_hw, nearest=True), params.resize_to, nearest=True)
+            return self._ops.relabel_u8(u8, self.background_id, self.n_class - 1)
         if self.img_shape is not None:
             lbl_u8 = self._ops.resize_u8(lbl_u8, self.img_shape, nearest=True)
         return self._ops.relabel_u8(lbl_u8, self.background_id, self.n_class - 1)

@@ -2345,6 +2345,85 @@ def relabel_u8(src, olabel, nlabel):
     return out
 
 
+def _joint_tables(params, n, device):
+    """(affine float64 [N,6], geom int32 [N,10]) on the device, from a ``mcdseg.augment.JointParams`` or a pair of tensors"""
+    affine, geom = params.tables(device) if hasattr(params, "tables") else params
+    affine, geom = _req(affine, "affine table", torch.float64), _req(geom, "geometry table", torch.int32)
+    if tuple(affine.shape) != (n, 6) or tuple(geom.shape) != (n, 10):
+        raise ValueError("mcdseg: the joint transform's tables must be [%d,6] and [%d,10], got %s and %s"
+                         % (n, n, tuple(affine.shape), tuple(geom.shape)))
+    return affine, geom
+
+
+def _joint_out_hw(out_hw):
+    oh, ow = int(out_hw[0]), int(out_hw[1])
+    if oh <= 0 or ow <= 0:
+        raise ValueError("mcdseg: the joint transform's output size must be positive, got %s" % (tuple(out_hw),))
+    return oh, ow
+
+
+def joint_augment_u8(src, params, out_hw, nearest=False):
+    """RandomHorizontallyFlip + RandomRotate + RandomCrop of joint_transforms.py:248-255 on the device, one gather pass, Pillow's bytes:
+    images (uint8 [N,H,W,C], ``Image.rotate(a, BILINEAR)``) -> uint8 [N,OH,OW,C]; label maps (``nearest=True``, uint8 [N,H,W],
+    ``Image.rotate(a, NEAREST)``) -> uint8 [N,OH,OW].  ``params``: the per-sample tables (``mcdseg.augment.JointParams``, or a pair
+    of device tensors: affine float64 [N,6], geom int32 [N,10]); ``out_hw`` = (OH, OW), the crop.  Pixels whose source lies outside
+    the image are 0 -- for a label map that is class 0, not the background id, as ``mask.rotate`` of the reference fills it."""
+    L = lib()
+    src = _req(src, "uint8 batch", torch.uint8)
+    oh, ow = _joint_out_hw(out_hw)
+    if nearest:
+        if src.dim() != 3:
+            raise TypeError("mcdseg: joint_augment_u8(nearest) takes a uint8 [N,H,W] tensor")
+        n, h, w = src.shape
+        _, geom = _joint_tables(params, n, src.device)
+        dst = torch.empty((n, oh, ow), dtype=torch.uint8, device=src.device)
+        check(L.mcdseg_joint_augment_label_u8(_p(src), _p(dst), _p(geom), n, h, w, oh, ow, _stream()), "joint_augment_label_u8")
+    else:
+        if src.dim() != 4:
+            raise TypeError("mcdseg: joint_augment_u8 takes a uint8 [N,H,W,C] tensor")
+        n, h, w, c = src.shape
+        affine, geom = _joint_tables(params, n, src.device)
+        dst = torch.empty((n, oh, ow, c), dtype=torch.uint8, device=src.device)
+        check(L.mcdseg_joint_augment_u8(_p(src), _p(dst), _p(affine), _p(geom), n, h, w, c, oh, ow, _stream()), "joint_augment_u8")
+    return dst
+
+
+def joint_augment_normalize_u8_(dst, src, params, mean, std, c_off=0):
+    """``joint_augment_u8`` and ``normalize_u8_`` in one pass: ``src`` uint8 [N,H,W,Cs] is flipped, rotated and cropped to the size of
+    ``dst`` [N,C,OH,OW] and written as fp32 into its channels [c_off, c_off+Cs).  A fill pixel is the normalised byte 0."""
+    src = _req(src, "uint8 image batch", torch.uint8)
+    if src.dim() != 4:
+        raise TypeError("mcdseg: joint_augment_normalize_u8_ takes a uint8 [N,H,W,C] tensor")
+    if dst.dtype != torch.float32 or not dst.is_contiguous() or not dst.is_cuda or dst.dim() != 4:
+        raise TypeError("mcdseg: joint_augment_normalize_u8_ writes into a contiguous fp32 [N,C,OH,OW] GPU tensor")
+    n, h, w, cs = src.shape
+    if dst.shape[0] != n:
+        raise ValueError("mcdseg: joint_augment_normalize_u8_ shape mismatch %s vs %s" % (tuple(src.shape), tuple(dst.shape)))
+    oh, ow = _joint_out_hw(dst.shape[2:])
+    affine, geom = _joint_tables(params, n, src.device)
+    mean, std = _req(mean.float(), "mean"), _req(std.float(), "std")
+    if mean.numel() < cs or std.numel() < cs:
+        raise ValueError("mcdseg: joint_augment_normalize_u8_ needs a mean and a std per source channel")
+    check(lib().mcdseg_joint_augment_normalize_u8(_p(src), _p(dst), _p(mean), _p(std), _p(affine), _p(geom), n, h, w, cs, oh, ow,
+                                                  dst.shape[1], int(c_off), _stream()), "joint_augment_normalize_u8")
+    return dst
+
+
+def joint_augment_relabel_u8(src, params, out_hw, olabel, nlabel):
+    """``joint_augment_u8(nearest=True)`` and ``relabel_u8`` in one pass: uint8 [N,H,W] label maps -> int64 [N,OH,OW].  The fill of
+    the rotation is label 0 (see ``joint_augment_u8``); ``olabel`` -> ``nlabel`` is applied after it, as ReLabel follows the rotation."""
+    src = _req(src, "uint8 label batch", torch.uint8)
+    if src.dim() != 3:
+        raise TypeError("mcdseg: joint_augment_relabel_u8 takes a uint8 [N,H,W] tensor")
+    n, h, w = src.shape
+    oh, ow = _joint_out_hw(out_hw)
+    _, geom = _joint_tables(params, n, src.device)
+    out = torch.empty((n, oh, ow), dtype=torch.int64, device=src.device)
+    check(lib().mcdseg_joint_augment_relabel_u8(_p(src), _p(out), _p(geom), n, h, w, oh, ow, int(olabel), int(nlabel), _stream()),
+          "joint_augment_relabel_u8")
+    return out
+
+
 def confusion_hist_(hist, gt, pred):
     """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated.  An entry
     whose prediction lies outside [0, n) is dropped too: it is not binned into a neighbouring row, as the reference's

@@ -35,6 +35,7 @@ class Run:
         torch.manual_seed(getattr(args, "seed", 1234))
         self._log = None
         self._pipe = None
+        self._joint = None  # (crop_size, rotate_angle) of the joint transform, set by ``train`` once the namespace is final
         self._args = args
 
     def images(self, t):
@@ -48,13 +49,39 @@ class Run:
             return self._pipeline().labels(t)
         return t.to(self.device, non_blocking=True)
 
+    def pair(self, img, lbl):
+        """a labelled batch -> device; raw uint8 image and label map go through the pipeline TOGETHER, so that a joint transform
+        (``--crop_size``) flips, rotates and crops both under one draw per sample"""
+        if img.dtype == torch.uint8 and lbl.dtype == torch.uint8:
+            return self._pipeline().joint(img, lbl)
+        return self.images(img), self.labels(lbl)
+
+    def joint_transform_args(self, args, trainer=None):
+        """(crop_size, rotate_angle) the pipeline is to apply.  The joint transform works on the raw uint8 batches (``--synthetic_raw``,
+        ``--src_file_list`` / ``--tgt_file_list``); fp32 ``--synthetic`` batches and a source with channels of its own (the triple
+        trainer's RGB+HHA+boundary, which has no raw form) keep ignoring the two flags, with one line that says so."""
+        crop, angle = getattr(args, "crop_size", -1), getattr(args, "rotate_angle", 0)
+        if crop <= 0:  # no joint transform at all, also with --rotate_angle set (adapt_trainer.py:101-102)
+            return -1, 0
+        raw = getattr(args, "synthetic_raw", False) or getattr(args, "src_file_list", None) or getattr(args, "tgt_file_list", None)
+        own_source = trainer is not None and trainer.src_input_ch not in (None, args.input_ch)
+        if not raw or own_source:
+            if self.is_main:
+                print("--crop_size %d --rotate_angle %s have no effect here: the joint transform runs on raw uint8 batches "
+                      "(--synthetic_raw, --src_file_list / --tgt_file_list)%s" % (crop, angle, ", and this trainer's source has no raw form" if own_source else ""))
+            return -1, 0
+        return crop, angle
+
     def _pipeline(self):
         if self._pipe is None:
             from datasets import DeviceInputPipeline
             lists = getattr(self._args, "src_file_list", None) or getattr(self._args, "tgt_file_list", None)
+            crop, angle = self._joint if self._joint is not None else (-1, 0)
             self._pipe = DeviceInputPipeline(self._args.input_ch, self._args.n_class, self.device,
                                              background_id=getattr(self._args, "background_id", 255),
-                                             img_shape=self._args.train_img_shape if lists else None)  # real files: Scale on the GPU
+                                             img_shape=self._args.train_img_shape if lists else None,  # real files: Scale on the GPU
+                                             crop_size=crop, rotate_angle=angle,
+                                             seed=getattr(self._args, "seed", 1234) + 101 * self.rank)  # per rank, as synthetic_spec shards
         return self._pipe
 
     @property
@@ -251,13 +278,14 @@ def train(trainer, args):
         for m in modules.values():
             fix_batchnorm_when_training(m)
     step = trainer.make_step(args, run, modules, optimizers)
+    run._joint = run.joint_transform_args(args, trainer)
 
     for epoch in range(start_epoch, args.epochs):
         sums = dict.fromkeys(trainer.sums, 0.0)
         it = enumerate(train_loader)
         for ind, batch in (tqdm.tqdm(it) if run.is_main else it):
             source, *targets = batch if adapt else (batch,)
-            losses = step(run.images(source[0]), run.labels(source[1]), *(run.images(t[0]) for t in targets), epoch=epoch)
+            losses = step(*run.pair(source[0], source[1]), *(run.images(t[0]) for t in targets), epoch=epoch)
             losses = dict(zip(trainer.sums, (float(v) for v in losses)))
             for name, value in losses.items():
                 sums[name] += value
