@@ -545,6 +545,27 @@ int mcdseg_joint_augment_label_u8(const uint8_t* src, uint8_t* dst, const int32_
 int mcdseg_joint_augment_relabel_u8(const uint8_t* src, int64_t* dst, const int32_t* geom, int32_t N, int32_t H, int32_t W, int32_t OH,
                                     int32_t OW, int32_t olabel, int32_t nlabel, void* stream);
 
+/* "Postprocess using Boundary Detection output" (sample_scripts/refine_seg_by_boundary.sh:15-17) on the device; all integer, exact.
+ *   boundary_regions:         tools/binalize_boundary.py:9-20 (m = boundary > thre, strictly, inside a frame of ones) and
+ *                             tools/apply_bwboundary.m:10-12 (bwboundaries: 8-connected objects, holes labelled, frame cropped):
+ *                             boundary uint8 [N,H,W] -> regions int32 [N,H,W].  Pixels are joined iff their mask bits are equal and they
+ *                             are 4-adjacent, or diagonal neighbours inside the mask.  regions = -1 for the frame object (every mask
+ *                             component with a pixel on the image border: MATLAB's label 1), else the smallest row-major index y*W+x of
+ *                             the pixel's component, per image.  Ids stay int32: the saturation at 255 of apply_bwboundary.m:15
+ *                             (imwrite(L/255)) is not reproduced.  Lock-free union-find inside `regions`; ws is not used and may be null.
+ *   refine_labels_by_regions: tools/refine_seg_by_bwboundary.py:34-42: out = the most common value of seg inside the pixel's region where
+ *                             min_thre < pixels of the region < max_thre (strict) and the id is >= 0, else seg; ties go to the value whose
+ *                             first pixel in row-major order comes earliest.  seg, out uint8 [N,H,W]; regions int32 [N,H,W], ANY map
+ *                             with ids in [-1, H*W) (an id outside is read as -1).  Votes are taken from seg; out must not alias it.
+ *   refine_workspace_bytes:   for refine_labels_by_regions, per image: 4*H*W (pixels per id, then its slot) + the vote table, one slot per
+ *                             id that can be eligible -- H*W / (max(min_thre, 0) + 1) of them -- x 256 label values x {pixels, first
+ *                             index} (8 bytes) + a winner byte per slot; each part padded to 16 bytes.  4-byte aligned. */
+size_t mcdseg_refine_workspace_bytes(int32_t N, int32_t H, int32_t W, int32_t min_thre);
+int mcdseg_boundary_regions(const uint8_t* boundary, int32_t thre, int32_t* regions, int32_t N, int32_t H, int32_t W, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int mcdseg_refine_labels_by_regions(const uint8_t* seg, const int32_t* regions, uint8_t* out, int32_t N, int32_t H, int32_t W,
+                                    int32_t min_thre, int32_t max_thre, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2-byte activation storage (round 6): BASELINE config 5 ("drn_d_105 ... bf16 ... HBM-bound stress"; the network is the reference's
  * Bottleneck trunk, models/drn.py:62-100, 344-348, trained by adapt_trainer.py:155-220).  In the one-term arithmetic MCDSEG_MATH_F16X1

@@ -9,6 +9,11 @@
 
 plus ``ave_ent_<x>.txt`` (mean entropy of pred_semseg1) and, when the data carry ground truth, ``eval_result.json``.
 
+With ``--refine_by_boundary`` the reference's "Postprocess using Boundary Detection output" (sample_scripts/refine_seg_by_boundary.sh)
+runs on the device while the batch is still there: ``refined_label/<name>`` = the label map with every region the boundary image
+encloses (``--boundary_thre``, ``--min_thre``, ``--max_thre``) set to its majority class, and ``eval_result_refined.json``
+({"before", "after"}, both at the test shape) when the data carry ground truth.
+
 The segmentation heads run at 1/8 resolution; the x8 bilinear up-sampling is fused into the argmax / entropy kernel
 (``mcdseg_predict_labels_up8``); the boundary map is one pass of ``mcdseg_boundary_head_fwd``.  pred_semseg2 is not evaluated: the reference computes it and drops it (its F2 average is commented out, :122-125), so
 ``--use_f2`` only renames the output directory, as there.  The palette visualisation (``vis/``) and ``eval.py`` run of the reference are
@@ -22,6 +27,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+import boundary_refine
 import tester_common
 from argmyparse import add_additional_params_to_args, get_da_mcd_testing_parser
 from models.model_util import get_segbd_multitask_models
@@ -30,8 +36,22 @@ from util import mkdir_if_not_exist
 from mcdseg import ops
 
 
+def get_parser():
+    parser = get_da_mcd_testing_parser()
+    g = parser.add_argument_group("refinement by the predicted boundaries (sample_scripts/refine_seg_by_boundary.sh)")
+    g.add_argument("--refine_by_boundary", action="store_true", help="also write refined_label/ (and eval_result_refined.json)")
+    g.add_argument("--boundary_thre", type=int, default=boundary_refine.DEFAULTS["thre"], help="threshold to binalize. Set from 0 to 255")
+    g.add_argument("--min_thre", type=int, default=boundary_refine.DEFAULTS["min_thre"], help="the minimum number of pixel in a region")
+    g.add_argument("--max_thre", type=int, default=boundary_refine.DEFAULTS["max_thre"], help="the maximum number of pixel in a region")
+    return parser
+
+
 def main(argv=None):
-    args = add_additional_params_to_args(get_da_mcd_testing_parser().parse_args(argv))
+    args = add_additional_params_to_args(get_parser().parse_args(argv))
+    refine = args.refine_by_boundary
+    if not refine:  # param.json of a run without the step stays what it was
+        for key in ("refine_by_boundary", "boundary_thre", "min_thre", "max_thre"):
+            delattr(args, key)
     t = tester_common.start(args)
     train_args = t.train_args
 
@@ -56,6 +76,8 @@ def main(argv=None):
     boundary_outdir = os.path.join(t.base_outdir, "boundary")
     mkdir_if_not_exist(label_outdir)
     mkdir_if_not_exist(boundary_outdir)
+    refiner = boundary_refine.BoundaryRefiner(t.base_outdir, args.boundary_thre, args.min_thre, args.max_thre, train_args.n_class,
+                                              t.dev) if refine else None
     total_ent, images = 0.0, 0
     with torch.no_grad():
         for imgs, gts, paths in t.loader:
@@ -69,12 +91,23 @@ def main(argv=None):
             tester_common.update_meter(t.meter, labels, gts, train_args.n_class)
             if args.saves_prob:
                 tester_common.save_probs(t.base_outdir, paths, ops.bilinear8(s1))
-            lab = ops.resize_u8(labels, t.test_img_shape, nearest=True).cpu().numpy()
+            lab_dev = ops.resize_u8(labels, t.test_img_shape, nearest=True)
+            lab = lab_dev.cpu().numpy()
             boundary = np.uint8(pred_boundary[:, 0].cpu().numpy() * 255)
+            resized = []
             for k, path in enumerate(paths):
                 name = os.path.basename(path)
                 Image.fromarray(lab[k]).save(os.path.join(label_outdir, name))
-                Image.fromarray(boundary[k]).resize(t.test_img_shape, Image.BILINEAR).save(os.path.join(boundary_outdir, name))
+                resized.append(Image.fromarray(boundary[k]).resize(t.test_img_shape, Image.BILINEAR))
+                resized[k].save(os.path.join(boundary_outdir, name))
+            if refiner is not None:  # on the bytes the boundary/ PNGs hold
+                refined = refiner.refine(lab_dev, np.stack([np.asarray(im) for im in resized]))
+                refiner.save(refined, [os.path.basename(path) for path in paths])
+                gt_u8 = boundary_refine.tester_ground_truth(gts, labels, train_args.n_class, t.test_img_shape)
+                if gt_u8 is not None:
+                    refiner.update(lab_dev, refined, gt_u8)
+    if refiner is not None:
+        refiner.finish()
     return label_outdir, boundary_outdir, tester_common.finish(t.base_outdir, total_ent, images, t.meter)
 
 

@@ -141,6 +141,9 @@ _SIGNATURES = {
     "mcdseg_joint_augment_normalize_u8": (c_int, [c_void_p] * 6 + [c_i32] * 8 + [c_void_p]),
     "mcdseg_joint_augment_label_u8": (c_int, [c_void_p] * 3 + [c_i32] * 5 + [c_void_p]),
     "mcdseg_joint_augment_relabel_u8": (c_int, [c_void_p] * 3 + [c_i32] * 7 + [c_void_p]),
+    "mcdseg_refine_workspace_bytes": (c_size_t, [c_i32] * 4),
+    "mcdseg_boundary_regions": (c_int, [c_void_p, c_i32, c_void_p] + [c_i32] * 3 + [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_refine_labels_by_regions": (c_int, [c_void_p] * 3 + [c_i32] * 5 + [c_void_p, c_size_t, c_void_p]),
     "mcdseg_scale_by_device_scalar": (c_int, [c_void_p, c_void_p, c_i64, c_void_p]),
     "mcdseg_sgd_momentum_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_float, c_float, c_float, c_float, c_void_p]),
     "mcdseg_adam_flat": (c_int, [c_void_p] * 4 + [c_i64] + [c_float] * 7 + [c_void_p]),

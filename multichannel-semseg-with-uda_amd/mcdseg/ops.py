@@ -2424,6 +2424,51 @@ def joint_augment_relabel_u8(src, params, out_hw, olabel, nlabel):
     return out
 
 
+def _req_maps(t, name, dtype):
+    t = _req(t, name, dtype)
+    if t.dim() != 3 or t.numel() == 0:
+        raise TypeError("mcdseg: %s must be a non-empty %s [N,H,W] tensor" % (name, dtype))
+    return t
+
+
+def boundary_regions(boundary_u8, thre):
+    """binalize_boundary.py:9-20 + bwboundaries (apply_bwboundary.m:10-12) on the device: uint8 boundary images [N,H,W] -> the
+    canonical int32 region map [N,H,W].  ``boundary > thre`` is the mask; mask pixels connect 8-wise, the others 4-wise; -1 = the
+    frame object (every mask component that touches the image border), else the smallest row-major index of the pixel's component."""
+    b = _req_maps(boundary_u8, "boundary batch", torch.uint8)
+    n, h, w = b.shape
+    regions = torch.empty((n, h, w), dtype=torch.int32, device=b.device)
+    with _timed("boundary_regions", (0, 5 * b.numel())):
+        check(lib().mcdseg_boundary_regions(_p(b), int(thre), _p(regions), n, h, w, None, ctypes.c_size_t(0), _stream()),
+              "boundary_regions")
+    return regions
+
+
+def refine_labels(seg_u8, regions, min_thre, max_thre):
+    """refine_seg_by_bwboundary.py:34-42 on the device: every region (ids >= 0 of an int32 map [N,H,W], canonical or not) of
+    ``min_thre < pixels < max_thre`` takes the most common value of ``seg_u8`` (uint8 [N,H,W]) inside it, ties to the value that occurs
+    first in row-major order; everything else keeps its label.  Returns a new uint8 [N,H,W] tensor."""
+    L = lib()
+    seg = _req_maps(seg_u8, "label batch", torch.uint8)
+    regions = _req_maps(regions, "region map", torch.int32)
+    if tuple(seg.shape) != tuple(regions.shape):
+        raise ValueError("mcdseg: refine_labels shape mismatch %s vs %s" % (tuple(seg.shape), tuple(regions.shape)))
+    n, h, w = seg.shape
+    nbytes = L.mcdseg_refine_workspace_bytes(n, h, w, int(min_thre))
+    ws = _ws(nbytes, seg.device)
+    out = torch.empty_like(seg)
+    with _timed("refine_labels_by_regions", (0, 10 * seg.numel())):
+        check(L.mcdseg_refine_labels_by_regions(_p(seg), _p(regions), _p(out), n, h, w, int(min_thre), int(max_thre), _p(ws),
+                                                ctypes.c_size_t(ws.numel() * 4), _stream()), "refine_labels_by_regions")
+    return out
+
+
+def refine_labels_by_boundary(seg_u8, boundary_u8, thre=50, min_thre=500, max_thre=79333):
+    """sample_scripts/refine_seg_by_boundary.sh:15-17 in one call (the reference's defaults): ``refine_labels`` over
+    ``boundary_regions(boundary_u8, thre)``"""
+    return refine_labels(seg_u8, boundary_regions(boundary_u8, thre), min_thre, max_thre)
+
+
 def confusion_hist_(hist, gt, pred):
     """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated.  An entry
     whose prediction lies outside [0, n) is dropped too: it is not binned into a neighbouring row, as the reference's
