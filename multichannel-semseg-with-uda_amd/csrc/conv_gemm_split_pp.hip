@@ -567,13 +567,7 @@ int compute_units() {  // one workgroup per CU: a launch is worth whole rounds o
   // option PP_CUS: a test plans a small batch as if the chip had fewer CUs, which gives it the rounds -- and hence the
   // launch plan -- of a batch that many times larger (BASELINE config 5's N = 32 plan at N = 2 with 16 "CUs")
   if (mcd_opt(MCD_OPT_PP_CUS) > 0) return (int)mcd_opt(MCD_OPT_PP_CUS);
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;  // MI355X
-    return cus;
-  }();
-  return n;
+  return mcdseg_internal_device_cus();
 }
 
 // MCDSEG_PINGPONG (development knob, read per call: a test runs one problem several ways): 0 the 4-wave tiles only; 1 whole rounds of
@@ -666,6 +660,17 @@ int pp_wide(const ConvSplitParams& p, int math, bool dgrad) {
 }
 
 }  // namespace
+
+// CUs of the current device, asked once (split.h; conv_wgrad_split_pp.hip plans with it as well)
+int mcdseg_internal_device_cus() {
+  static const int n = [] {
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+      cus = 256;  // MI355X
+    return cus;
+  }();
+  return n;
+}
 
 // 1 when the whole convolution runs on the 256 x 320 ping-pong tile (BatchNorm partial rows of 160 pixels)
 int mcdseg_internal_conv_pp_wide(const ConvSplitParams& p, int math, bool dgrad) { return pp_wide(p, math, dgrad); }

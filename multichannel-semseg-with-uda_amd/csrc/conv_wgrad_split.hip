@@ -426,7 +426,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   constexpr int KK = NQD / 4;                // K = 16 blocks per stage
   constexpr int AB = BM / 128;               // 128-channel blocks of the dY tile
   typedef typename P::frag frag;
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
   constexpr int QUAD = 1024;                 // bytes one DMA instruction deposits: [cg 16][pixel 4][16 B]
   constexpr int A_UNIT = NQD * AB * QUAD;    // one piece of the dY tile: [quad][cg 16 AB][pixel 4][16 B]
   constexpr int B_UNIT = NQD * QUAD;
@@ -486,6 +485,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   const int nblk = opnd ? 1 : AB;                          // 128-row blocks this wave moves per quad
   const int sHW = sH * sW;
   // the descriptor covers this wave's PIECE and starts `bias` bytes below it so that the SGPR offset (tile + tap shift) is never negative
+  // (written out, as in conv_wgrad_split_cb_kernel: through mcd_piece_rsrc of split.h this kernel's 256 x 128 form compiles to other code)
   const int bias = p.pad * 16 + 16;
   const char* sptr = (const char*)(isx ? p.x_cb : p.dy_cb) + piece * (isx ? p.x_piece_stride : p.dy_piece_stride) - bias;
   const int sbytes = (isx ? p.x_cb_bytes : p.dy_cb_bytes) + bias;
@@ -553,21 +553,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   const int a_lane = (wm * 4 * WM) * 64 + trow;  // the wave's first channel group: 4 WM groups per wave
   const int b_lane = (wn * 4 * WN) * 64 + trow;
 
-  auto tr_read = [&](const unsigned char* addr) -> s16x4 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(addr));
-#else
-    (void)addr;
-    return s16x4{};
-#endif
-  };
-  auto load_frag = [&](const unsigned char* unit, int quad_bytes, int quad0, int lane_off, int i) -> frag {
-    const s16x4 lo = tr_read(unit + quad0 * quad_bytes + lane_off + i * 256);
-    const s16x4 hi = tr_read(unit + (quad0 + 1) * quad_bytes + lane_off + i * 256);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(frag, v);
-  };
   // Two fragment sets: while the matrix instructions of tile s run on one, the transposing reads of tile s+1 fill the other
   // (MCD_WGRAD_PIPE, default).  Without it a wave spends the LDS round trip of 24 reads at the head of every 16-pixel stage
   // before its first MFMA -- measured through the one-term policy: with a third of the matrix work the 256 x 128 kernel only
@@ -577,43 +562,20 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr_kernel(WgradCbPara
   //   reads tile s+1's fragments, multiplies tile s, then waits for tile s+2 and its own reads and meets the barrier.
   static_assert(KK == 1, "one K = 16 block per stage");
   frag fa[2][NP][WM], fb[2][NP][WN];
-  // The transposing reads are issued as inline assembly: for a compiler-visible LDS load the wait-count pass puts an
-  // s_waitcnt vmcnt(0) in front whenever an LDS-DMA may be pending (it cannot tell that the DMA targets another stage), which
-  // would drain the prefetch every step.  Their completion is the lgkmcnt(0) of the step's closing wait; `settle` then
-  // re-defines the registers behind that wait so that no consumer can be scheduled ahead of it.
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  auto tr_read_at = [&](unsigned base, auto off_c) -> s16x4 {
-    s16x4 v;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"(decltype(off_c)::value) : "memory");
-#else
-    (void)base;
-    v = s16x4{};
-#endif
-    return v;
-  };
+  // (the transposing reads are inline assembly -- mcd_tr_read_at, split.h; they complete at the lgkmcnt(0) of the step's closing wait
+  // and mcd_settle re-defines their registers behind it)
   auto read_frags = [&](int stage, auto set_c) {
     constexpr int SET = decltype(set_c)::value;
-#if defined(__HIP_DEVICE_COMPILE__)
-    const unsigned sbase = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem + (unsigned)(stage * STAGE);
-#else
-    const unsigned sbase = 0;
-#endif
+    const unsigned sbase = mcd_lds_addr(smem) + (unsigned)(stage * STAGE);
     const unsigned base_a = sbase + (unsigned)((2 * lh) * AB * QUAD + a_lane);
     const unsigned base_b = sbase + (unsigned)(NP * A_UNIT + (2 * lh) * QUAD + b_lane);
-    auto frag_of = [&](unsigned base, auto lo_c, auto hi_c) -> frag {
-      const s16x4 lo = tr_read_at(base, lo_c);
-      const s16x4 hi = tr_read_at(base, hi_c);
-      const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-      return __builtin_bit_cast(frag, v);
-    };
     // (compile-time offsets: piece, 32-row block, second quad)
 #define MCD_A_FRAG(PC, I) \
     if constexpr ((PC) < P::NPU && (I) < WM) \
-      fa[SET][PC][I] = frag_of(base_a, std::integral_constant<int, (PC) * A_UNIT + (I) * 256>{}, std::integral_constant<int, (PC) * A_UNIT + (I) * 256 + AB * QUAD>{});
+      fa[SET][PC][I] = mcd_tr_frag<frag, (PC) * A_UNIT + (I) * 256, (PC) * A_UNIT + (I) * 256 + AB * QUAD>(base_a);
 #define MCD_B_FRAG(PC, J) \
     if constexpr ((PC) < P::NPU && (J) < WN) \
-      fb[SET][PC][J] = frag_of(base_b, std::integral_constant<int, (PC) * B_UNIT + (J) * 256>{}, std::integral_constant<int, (PC) * B_UNIT + (J) * 256 + QUAD>{});
+      fb[SET][PC][J] = mcd_tr_frag<frag, (PC) * B_UNIT + (J) * 256, (PC) * B_UNIT + (J) * 256 + QUAD>(base_b);
     MCD_A_FRAG(0, 0) MCD_A_FRAG(0, 1) MCD_A_FRAG(0, 2) MCD_A_FRAG(0, 3)
     MCD_B_FRAG(0, 0) MCD_B_FRAG(0, 1)
     MCD_A_FRAG(1, 0) MCD_A_FRAG(1, 1) MCD_A_FRAG(1, 2) MCD_A_FRAG(1, 3)
@@ -737,7 +699,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr64_kernel(WgradCbPa
   constexpr int NP = P::NP;
   constexpr int NQD = 2 * R, KK = NQD / 4;
   typedef typename P::frag frag;
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
   constexpr int AQ = 512, BQ = 1024;         // bytes per quad image: [cg 8][pixel 4][16 B] / [tap 2][cg 8][pixel 4][16 B]
   constexpr int A_UNIT = NQD * AQ, B_UNIT = NQD * BQ;
   constexpr int STAGE = NP * (A_UNIT + B_UNIT);  // 24 KB
@@ -841,20 +802,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_split_tr64_kernel(WgradCbPa
   const int a_lane = (wm * 4) * 64 + trow;  // 32 co = 4 channel groups of the 8 in a dY quad
   const int b_lane = (wn * 8) * 64 + trow;  // tap wn: its 8 channel groups of the 16 in an X quad
 
-  auto tr_read = [&](const unsigned char* addr) -> s16x4 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(addr));
-#else
-    (void)addr;
-    return s16x4{};
-#endif
-  };
   auto load_frag = [&](const unsigned char* unit, int quad_bytes, int quad0, int lane_off) -> frag {
-    const s16x4 lo = tr_read(unit + quad0 * quad_bytes + lane_off);
-    const s16x4 hi = tr_read(unit + (quad0 + 1) * quad_bytes + lane_off);
-    typedef short s16x8 __attribute__((ext_vector_type(8)));
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(frag, v);
+    return mcd_frag_pack<frag>(mcd_tr_read(unit + quad0 * quad_bytes + lane_off), mcd_tr_read(unit + (quad0 + 1) * quad_bytes + lane_off));
   };
   frag fa[NP], fb[NP][2];
   auto read_frags = [&](const unsigned char* st, int kk) {
@@ -950,8 +899,8 @@ int mcdseg_internal_wgrad_split_cb_launch(const mcdseg_conv_desc* d, int math, c
   }
   p.x_cb_bytes = (int)xb;
   p.dy_cb_bytes = (int)yb;
-  p.x_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cin * d->H * d->W * 2;  // (F16X1 reads piece 0 only)
-  p.dy_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cout * d->Ho * d->Wo * 2;
+  p.x_piece_stride = mcd_piece_stride(d, math, (long long)d->Cin * d->H * d->W);
+  p.dy_piece_stride = mcd_piece_stride(d, math, (long long)d->Cout * d->Ho * d->Wo);
   const int64_t per_split = (int64_t)(co_p / (big ? 256 : 128)) * (ci_p / 128) * d->KH * d->KW;
   const int64_t nwg = 8 * ceil_div64(splits, 8) * per_split;
   if (nwg >= (1ll << 31)) {
@@ -992,8 +941,8 @@ int mcdseg_internal_wgrad_split_tr64_launch(const mcdseg_conv_desc* d, int math,
   }
   p.x_cb_bytes = (int)xb;
   p.dy_cb_bytes = (int)yb;
-  p.x_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cin * d->H * d->W * 2;  // (F16X1 reads piece 0 only)
-  p.dy_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cout * d->Ho * d->Wo * 2;
+  p.x_piece_stride = mcd_piece_stride(d, math, (long long)d->Cin * d->H * d->W);
+  p.dy_piece_stride = mcd_piece_stride(d, math, (long long)d->Cout * d->Ho * d->Wo);
   const int64_t per_split = (int64_t)(co_p / 64) * (ci_p / 64) * ((d->KH * d->KW + 1) / 2);
   const int64_t nwg = 8 * ceil_div64(splits, 8) * per_split;
   if (nwg >= (1ll << 31)) {

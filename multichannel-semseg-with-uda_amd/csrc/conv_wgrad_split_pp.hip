@@ -30,7 +30,6 @@
 // keep their order and a slab of dead steps only is written as zeros, so the slab reduction adds what it added before, bit for bit.
 // The one difference: an Inf or NaN in dZ gave NaN (Inf * 0) in a skipped step of the full loop, and contributes nothing here.
 #include <cstdlib>
-#include <type_traits>
 
 #include "split.h"
 
@@ -91,6 +90,15 @@ struct LiveRows {
   }
 };
 
+// ---- what the two kernels below share -------------------------------------------------------------------------------------------
+constexpr int NDMA = 4;            // DMA instructions per (operand, piece, block) and stage: 4 channel groups x 16 pixels each
+constexpr int DSTR = 1024 + 64;    // bytes from one instruction's image [group 4][pixel 16][16 B] to the next (64 B: the bank offset)
+constexpr int BLKB = NDMA * DSTR;  // one 128-channel block of one piece
+constexpr int NS = 3;              // stages
+
+// consecutive workgroup numbers on one XCD (the dispatcher deals blockIdx round-robin over the 8 XCDs; the grid is a multiple of 8)
+__device__ __forceinline__ int pp_workgroup() { return (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3); }
+
 template <class P>
 __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams p) {
   static_assert(P::NP == 2, "two-piece policies");
@@ -98,14 +106,8 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
   constexpr int NP = P::NP;
   constexpr int NBLK = 2;               // 128-channel blocks per operand
   typedef typename P::frag frag;
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  constexpr int NDMA = 4;               // DMA instructions per (operand, piece, block) and stage: 4 channel groups x 16 pixels each
-  constexpr int DSTR = 1024 + 64;       // bytes from one instruction's image [group 4][pixel 16][16 B] to the next (64 B: the bank offset)
-  constexpr int BLKB = NDMA * DSTR;     // one 128-channel block of one piece
   constexpr int UNIT = NBLK * BLKB;     // one piece of one operand
   constexpr int STAGE = 2 * NP * UNIT;  // [operand: dZ, X][piece]
-  constexpr int NS = 3;
   static_assert(NS * STAGE <= 160 * 1024, "LDS");
   // One-term arithmetic, policy SplitF16x1D (the second piece of neither operand is ever moved): the idle piece-1 slots of the three
   // stages are three MORE stages -- logical stage c sits at (c % 3) * STAGE + (c / 3) * UNIT of both operands -- and a barrier interval
@@ -126,8 +128,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
   const int l31 = lane & 31, lh = lane >> 5;
   const int T_ = p.KH * p.KW;
 
-  // consecutive workgroup numbers on one XCD (the dispatcher deals blockIdx round-robin over the 8 XCDs; the grid is a multiple of 8)
-  const int w_id = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const int w_id = pp_workgroup();
   if (w_id >= p.nwg) return;
   const int tiles_all = p.co_tiles * p.ci_tiles * T_;
   const long long total = (long long)tiles_all * p.kt;
@@ -152,11 +153,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
   const int sS = isx ? p.stride : 1;
   const int sC8 = (isx ? p.Cin : p.Cout) >> 3;
   const int sHW = sH * sW;
-  // the descriptor covers this wave's PIECE and starts `bias` bytes below it so that the SGPR offset (tile + tap shift) is never negative
-  const int bias = p.pad * 16 + 16;
-  const char* sptr = (const char*)(isx ? p.x_cb : p.dy_cb) + piece * (isx ? p.x_piece_stride : p.dy_piece_stride) - bias;
-  const int sbytes = (isx ? p.x_cb_bytes : p.dy_cb_bytes) + bias;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)sptr, 0, sbytes, 0x00020000);
+  const int bias = mcd_piece_bias(p.pad);
+  const __amdgpu_buffer_rsrc_t rs =  // (this wave's PIECE)
+      mcd_piece_rsrc(isx ? p.x_cb : p.dy_cb, piece * (isx ? p.x_piece_stride : p.dy_piece_stride), isx ? p.x_cb_bytes : p.dy_cb_bytes, bias);
   constexpr unsigned OOB = 0x80000000u;
   const int lane_x = px * sS;
   unsigned char* const unit_lds = smem + (opnd * NP + piece) * UNIT + blk * BLKB;
@@ -172,31 +171,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
   const int a_lane = wm * BLKB + trow;                          // the wave's 128 dZ channels = block wm
   const int b_lane = (wn >> 1) * BLKB + (wn & 1) * 512 + trow;  // its 64 X channels = rows 2 (wn & 1), 2 (wn & 1) + 1 of block wn >> 1
 
-  // The transposing reads are issued as inline assembly: for a compiler-visible one the wait-count pass puts an s_waitcnt vmcnt(0) in
-  // front whenever an LDS-DMA may be pending (it cannot tell that the DMA targets another stage), which would drain the prefetch at the
-  // head of every read phase.  They complete at the lgkmcnt(0) of the wait that closes the read phase; `settle` re-defines the registers
-  // behind that wait so that no matrix instruction can be scheduled ahead of it.
-  auto tr_read_at = [&](unsigned base, auto off_c) -> s16x4 {
-    s16x4 v;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"(decltype(off_c)::value) : "memory");
-#else
-    (void)base;
-    v = s16x4{};
-#endif
-    return v;
-  };
-  auto frag_of = [&](unsigned base, auto lo_c, auto hi_c) -> frag {  // k slots 0-3 from this lane's first quad, 4-7 from its second
-    const s16x4 lo = tr_read_at(base, lo_c);
-    const s16x4 hi = tr_read_at(base, hi_c);
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(frag, v);
-  };
-#if defined(__HIP_DEVICE_COMPILE__)
-  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
-#else
-  const unsigned smem_lds = 0;
-#endif
+  const unsigned smem_lds = mcd_lds_addr(smem);  // (the transposing reads are inline assembly: mcd_tr_read_at, split.h)
 
   while (g_next < g_end) {  // the segments of this workgroup's piece: the rest of the current tile's K range, at most
     int tile, k0, k1, slab_id;
@@ -287,9 +262,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
         const unsigned off0 = (unsigned)stage_off(2 * dcur), off1 = (unsigned)stage_off(2 * dcur + 1);
         const unsigned a0 = smem_lds + off0 + (unsigned)a_lane, b0 = smem_lds + off0 + (unsigned)b_lane;
         const unsigned a1 = smem_lds + off1 + (unsigned)a_lane, b1 = smem_lds + off1 + (unsigned)b_lane;
-#define MCD_A2(U, BASE, I) fa2[U][I] = frag_of(BASE, std::integral_constant<int, (I) * 256>{}, std::integral_constant<int, (I) * 256 + 64>{});
+#define MCD_A2(U, BASE, I) fa2[U][I] = mcd_tr_frag<frag, (I) * 256, (I) * 256 + 64>(BASE);
 #define MCD_B2(U, BASE, J) \
-        fb2[U][J] = frag_of(BASE, std::integral_constant<int, NP * UNIT + (J) * 256>{}, std::integral_constant<int, NP * UNIT + (J) * 256 + 64>{});
+        fb2[U][J] = mcd_tr_frag<frag, NP * UNIT + (J) * 256, NP * UNIT + (J) * 256 + 64>(BASE);
         MCD_A2(0, a0, 0) MCD_A2(0, a0, 1) MCD_A2(0, a0, 2) MCD_A2(0, a0, 3) MCD_B2(0, b0, 0) MCD_B2(0, b0, 1)
         MCD_A2(1, a1, 0) MCD_A2(1, a1, 1) MCD_A2(1, a1, 2) MCD_A2(1, a1, 3) MCD_B2(1, b1, 0) MCD_B2(1, b1, 1)
 #undef MCD_A2
@@ -346,10 +321,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp_kernel(WgradPpParams 
         // (compile-time offsets: operand, piece, 32-row block, second quad)
 #define MCD_A_FRAG(PC, I) \
         if constexpr ((PC) < P::NPU) \
-          fa[PC][I] = frag_of(base_a, std::integral_constant<int, (PC) * UNIT + (I) * 256>{}, std::integral_constant<int, (PC) * UNIT + (I) * 256 + 64>{});
+          fa[PC][I] = mcd_tr_frag<frag, (PC) * UNIT + (I) * 256, (PC) * UNIT + (I) * 256 + 64>(base_a);
 #define MCD_B_FRAG(PC, J) \
         if constexpr ((PC) < P::NPU) \
-          fb[PC][J] = frag_of(base_b, std::integral_constant<int, (NP + (PC)) * UNIT + (J) * 256>{}, std::integral_constant<int, (NP + (PC)) * UNIT + (J) * 256 + 64>{});
+          fb[PC][J] = mcd_tr_frag<frag, (NP + (PC)) * UNIT + (J) * 256, (NP + (PC)) * UNIT + (J) * 256 + 64>(base_b);
         MCD_A_FRAG(0, 0) MCD_A_FRAG(0, 1) MCD_A_FRAG(0, 2) MCD_A_FRAG(0, 3) MCD_B_FRAG(0, 0) MCD_B_FRAG(0, 1)
         MCD_A_FRAG(1, 0) MCD_A_FRAG(1, 1) MCD_A_FRAG(1, 2) MCD_A_FRAG(1, 3) MCD_B_FRAG(1, 0) MCD_B_FRAG(1, 1)
 #undef MCD_A_FRAG
@@ -469,13 +444,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
   constexpr int WM = 2, WN = 3;
   constexpr int NP = P::NP;
   typedef typename P::frag frag;
-  typedef short s16x4 __attribute__((ext_vector_type(4)));
-  typedef short s16x8 __attribute__((ext_vector_type(8)));
-  constexpr int NDMA = 4;
-  constexpr int DSTR = 1024 + 64;
-  constexpr int BLKB = NDMA * DSTR;     // one 128-channel block of one piece
   constexpr int STAGE = 8 * BLKB;       // [dZ piece 0][dZ piece 1][X piece 0: kx 0, 1, 2][X piece 1: kx 0, 1, 2]
-  constexpr int NS = 3;
   static_assert(NS * STAGE <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) unsigned char smem[NS * STAGE];
 
@@ -486,7 +455,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
   const int wm = grp_id, wn = wave & 3;
   const int l31 = lane & 31, lh = lane >> 5;
 
-  const int w_id = (blockIdx.x & 7) * (gridDim.x >> 3) + (blockIdx.x >> 3);
+  const int w_id = pp_workgroup();
   if (w_id >= p.nwg) return;
   const int tiles_all = p.co_tiles * p.ci_tiles * p.KH;
 
@@ -501,10 +470,9 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
   const int sS = isx ? p.stride : 1;
   const int sC8 = (isx ? p.Cin : p.Cout) >> 3;
   const int sHW = sH * sW;
-  const int bias = p.pad * 16 + 16;
-  const char* sptr = (const char*)(isx ? p.x_cb : p.dy_cb) + piece * (isx ? p.x_piece_stride : p.dy_piece_stride) - bias;
-  const int sbytes = (isx ? p.x_cb_bytes : p.dy_cb_bytes) + bias;
-  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)sptr, 0, sbytes, 0x00020000);
+  const int bias = mcd_piece_bias(p.pad);
+  const __amdgpu_buffer_rsrc_t rs =  // (this wave's PIECE)
+      mcd_piece_rsrc(isx ? p.x_cb : p.dy_cb, piece * (isx ? p.x_piece_stride : p.dy_piece_stride), isx ? p.x_cb_bytes : p.dy_cb_bytes, bias);
   constexpr unsigned OOB = 0x80000000u;
   const int lane_x = px * sS;
   unsigned char* const unit_lds = smem + (isx ? (2 + piece * 3 + kxs) : piece) * BLKB;
@@ -522,27 +490,7 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
     b_lane[j] = (2 + (col0 >> 7)) * BLKB + ((col0 & 127) >> 5) * 256 + trow;
   }
 
-  auto tr_read_at = [&](unsigned base, auto off_c) -> s16x4 {
-    s16x4 v;
-#if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"(decltype(off_c)::value) : "memory");
-#else
-    (void)base;
-    v = s16x4{};
-#endif
-    return v;
-  };
-  auto frag_of = [&](unsigned base, auto lo_c, auto hi_c) -> frag {
-    const s16x4 lo = tr_read_at(base, lo_c);
-    const s16x4 hi = tr_read_at(base, hi_c);
-    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(frag, v);
-  };
-#if defined(__HIP_DEVICE_COMPILE__)
-  const unsigned smem_lds = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)smem;
-#else
-  const unsigned smem_lds = 0;
-#endif
+  const unsigned smem_lds = mcd_lds_addr(smem);
 
   for (int item = w_id; item < p.items; item += p.nwg) {  // slab plan: item = (K slab item / tiles, tile item % tiles)
     const int sl = item / tiles_all;
@@ -615,10 +563,10 @@ __global__ __launch_bounds__(512) void conv_wgrad_split_pp3_kernel(WgradPpParams
                      base_b2 = smem_lds + (unsigned)(cur * STAGE + b_lane[2]);
 #define MCD_A3_FRAG(PC, I) \
       if constexpr ((PC) < P::NPU) \
-        fa[PC][I] = frag_of(base_a, std::integral_constant<int, (PC) * BLKB + (I) * 256>{}, std::integral_constant<int, (PC) * BLKB + (I) * 256 + 64>{});
+        fa[PC][I] = mcd_tr_frag<frag, (PC) * BLKB + (I) * 256, (PC) * BLKB + (I) * 256 + 64>(base_a);
 #define MCD_B3_FRAG(PC, J, BASE) \
       if constexpr ((PC) < P::NPU) \
-        fb[PC][J] = frag_of(BASE, std::integral_constant<int, (PC) * 3 * BLKB>{}, std::integral_constant<int, (PC) * 3 * BLKB + 64>{});
+        fb[PC][J] = mcd_tr_frag<frag, (PC) * 3 * BLKB, (PC) * 3 * BLKB + 64>(BASE);
       MCD_A3_FRAG(0, 0) MCD_A3_FRAG(0, 1) MCD_B3_FRAG(0, 0, base_b0) MCD_B3_FRAG(0, 1, base_b1) MCD_B3_FRAG(0, 2, base_b2)
       MCD_A3_FRAG(1, 0) MCD_A3_FRAG(1, 1) MCD_B3_FRAG(1, 0, base_b0) MCD_B3_FRAG(1, 1, base_b1) MCD_B3_FRAG(1, 2, base_b2)
 #undef MCD_A3_FRAG
@@ -710,13 +658,52 @@ __global__ __launch_bounds__(256) void wgrad_reduce_rt_kernel(const float* __res
 int pp_compute_units() {
   if (mcd_opt(MCD_OPT_WGRAD_PP_CUS) > 0) return (int)mcd_opt(MCD_OPT_WGRAD_PP_CUS);  // development knob: plan the weight gradient for fewer CUs than the chip has
   if (mcd_opt(MCD_OPT_PP_CUS) > 0) return (int)mcd_opt(MCD_OPT_PP_CUS);              // development knob (shared with conv_gemm_split_pp.hip)
-  static const int n = [] {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-      cus = 256;  // MI355X
-    return cus;
-  }();
-  return n;
+  return mcdseg_internal_device_cus();
+}
+
+// The slab plan of a layer of `tiles` tiles of `kt` K-steps each on `nwg` workgroups: K-steps per slab `ls`, slabs `ns` (0: none), and the
+// share `eff` of the workgroups' time that is work.  Rounds of items per workgroup: the fewest whose slabs keep >= 95 % of the CUs busy
+// (else the best of up to four).
+struct SlabPlan {
+  int64_t ls = 0, ns = 0;
+  double eff = 0.0;
+};
+SlabPlan slab_plan(int64_t kt, int64_t tiles, int64_t nwg) {
+  const int64_t total = tiles * kt;
+  SlabPlan best;
+  for (int64_t r = 1; r <= 4; ++r) {
+    int64_t ns = r * nwg / tiles;
+    if (ns < 1) continue;
+    if (ns > kt / 32) ns = kt / 32;  // (an item of less than 32 K-steps is all prologue)
+    if (ns < 1) continue;
+    const int64_t ls = ceil_div64(kt, ns);
+    ns = ceil_div64(kt, ls);
+    const double eff = (double)total / ((double)nwg * (double)(ceil_div64(ns * tiles, nwg) * ls));
+    if (eff > best.eff + 0.02 || best.ns == 0) best.ls = ls, best.ns = ns, best.eff = eff;
+    if (best.eff >= 0.95) break;
+  }
+  return best;
+}
+
+// The kernels' parameters from the descriptor; `edge` = the tile's channels per side (256 or 128).  p.items is the caller's (its tiles).
+int fill_params(WgradPpParams& p, const char* name, const mcdseg_conv_desc* d, int math, const void* x_cb, const void* dy_cb, float* slab, int edge,
+                int L, int nwg, int slabs) {
+  const int64_t xb = (int64_t)d->N * d->Cin * d->H * d->W * 2, yb = (int64_t)d->N * d->Cout * d->Ho * d->Wo * 2;
+  MCD_REQUIRE(xb + 4096 < (1ll << 31) && yb + 4096 < (1ll << 31) && (d->Ncb == 0 || d->Ncb >= d->N),
+              "%s: pre-split operands need < 2 GiB per operand piece and Ncb >= N", name);
+  p.x_cb = x_cb; p.dy_cb = dy_cb; p.slab = slab;
+  p.N = d->N; p.Cin = d->Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.Ho = d->Ho; p.Wo = d->Wo;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
+  p.co_tiles = ceil_div(d->Cout, edge); p.ci_tiles = ceil_div(d->Cin, edge);
+  p.tiles_x = ceil_div(d->Wo, 16); p.tiles_y = d->Ho;
+  p.kt = d->N * p.tiles_x * p.tiles_y;
+  p.L = L; p.nwg = nwg;
+  p.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
+  p.slabs = slabs;
+  p.x_cb_bytes = (int)xb; p.dy_cb_bytes = (int)yb;
+  p.x_piece_stride = mcd_piece_stride(d, math, (long long)d->Cin * d->H * d->W);
+  p.dy_piece_stride = mcd_piece_stride(d, math, (long long)d->Cout * d->Ho * d->Wo);
+  return 0;
 }
 
 }  // namespace
@@ -747,25 +734,12 @@ int mcdseg_internal_wgrad_pp_plan(const mcdseg_conv_desc* d, int math, int* L, s
   int64_t nwg = pp_compute_units();
   if (total < nwg * 32) return 0;  // (less than 32 K-steps per CU: the launch is all prologue and slab traffic)
   if (!stream_k) {
-    // rounds of items per workgroup: the fewest whose slabs keep >= 95 % of the CUs busy (else the best of up to four)
-    int64_t best_r = 0, best_ls = 0, best_ns = 0;
-    double best_eff = 0.0;
-    for (int64_t r = 1; r <= 4; ++r) {
-      int64_t ns = r * nwg / tiles;
-      if (ns < 1) continue;
-      if (ns > kt / 32) ns = kt / 32;  // (an item of less than 32 K-steps is all prologue)
-      if (ns < 1) continue;
-      const int64_t ls = ceil_div64(kt, ns);
-      ns = ceil_div64(kt, ls);
-      const double eff = (double)total / ((double)nwg * (double)(ceil_div64(ns * tiles, nwg) * ls));
-      if (eff > best_eff + 0.02 || best_r == 0) best_r = r, best_ls = ls, best_ns = ns, best_eff = eff;
-      if (best_eff >= 0.95) break;
-    }
-    if (best_r > 0 && best_eff >= 0.80) {
-      const int64_t items = best_ns * tiles;
+    const SlabPlan sp = slab_plan(kt, tiles, nwg);
+    if (sp.ns > 0 && sp.eff >= 0.80) {
+      const int64_t items = sp.ns * tiles;
       const int64_t rounds = ceil_div64(items, nwg);
-      if (L) *L = (int)best_ls;
-      if (slabs_out) *slabs_out = (int)best_ns;
+      if (L) *L = (int)sp.ls;
+      if (slabs_out) *slabs_out = (int)sp.ns;
       if (slab_floats) *slab_floats = (size_t)items * 256 * 256;
       return (int)ceil_div64(items, rounds);
     }
@@ -784,21 +758,10 @@ int mcdseg_internal_wgrad_pp_launch(const mcdseg_conv_desc* d, int math, const v
   int L = 0, slabs = 0;
   const int nwg = mcdseg_internal_wgrad_pp_plan(d, math, &L, nullptr, &slabs);
   MCD_REQUIRE(nwg > 0, "conv_wgrad_split_pp: the geometry has no stream-K plan");
-  const int64_t xb = (int64_t)d->N * d->Cin * d->H * d->W * 2, yb = (int64_t)d->N * d->Cout * d->Ho * d->Wo * 2;
-  MCD_REQUIRE(xb + 4096 < (1ll << 31) && yb + 4096 < (1ll << 31) && (d->Ncb == 0 || d->Ncb >= d->N),
-              "conv_wgrad_split_pp: pre-split operands need < 2 GiB per operand piece and Ncb >= N");
-  p.x_cb = x_cb; p.dy_cb = dy_cb; p.slab = slab;
-  p.N = d->N; p.Cin = d->Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.Ho = d->Ho; p.Wo = d->Wo;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.co_tiles = ceil_div(d->Cout, 256); p.ci_tiles = ceil_div(d->Cin, 256);
-  p.tiles_x = ceil_div(d->Wo, 16); p.tiles_y = d->Ho;
-  p.kt = d->N * p.tiles_x * p.tiles_y;
-  p.L = L; p.nwg = nwg;
-  p.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
-  p.slabs = slabs; p.items = slabs * p.co_tiles * p.ci_tiles * d->KH * d->KW;
-  p.x_cb_bytes = (int)xb; p.dy_cb_bytes = (int)yb;
-  p.x_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cin * d->H * d->W * 2;  // (F16X1 reads piece 0 only)
-  p.dy_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cout * d->Ho * d->Wo * 2;
+  if (const int e = fill_params(p, "conv_wgrad_split_pp", d, math, x_cb, dy_cb, slab, 256, L, nwg, slabs)) return e;
+  const int T = d->KH * d->KW;
+  const int tiles_all = p.co_tiles * p.ci_tiles * T;
+  p.items = slabs * tiles_all;
   const dim3 grid((unsigned)(8 * ceil_div(nwg, 8)));
   if (math == MCDSEG_MATH_F16X1 && mcd_opt(MCD_OPT_WGRAD_PP_DEEP) != 0)
     hipLaunchKernelGGL(conv_wgrad_split_pp_kernel<SplitF16x1D>, grid, dim3(512), 0, st, p);  // six logical stages (see the kernel)
@@ -807,10 +770,9 @@ int mcdseg_internal_wgrad_pp_launch(const mcdseg_conv_desc* d, int math, const v
   else
     hipLaunchKernelGGL(conv_wgrad_split_pp_kernel<SplitF16x3>, grid, dim3(512), 0, st, p);
   MCD_LAUNCH_CHECK("conv_wgrad_split_pp");
-  const int T = d->KH * d->KW;
   MCD_REQUIRE(T <= 33, "conv_wgrad_split_pp: more than 33 taps");
   hipLaunchKernelGGL(wgrad_reduce_sk_kernel, dim3((unsigned)ceil_div(d->Cin, 64), (unsigned)d->Cout), dim3(256), 0, st, (const float*)slab, dw, d->Cout,
-                     d->Cin, T, p.ci_tiles, p.kt, L, slabs, p.co_tiles * p.ci_tiles * T, x_bound, dy_bound);
+                     d->Cin, T, p.ci_tiles, p.kt, L, slabs, tiles_all, x_bound, dy_bound);
   MCD_LAUNCH_CHECK("wgrad_reduce_sk");
   return 0;
 }
@@ -831,25 +793,13 @@ int mcdseg_internal_wgrad_pp3_plan(const mcdseg_conv_desc* d, int math, int* L, 
   const int64_t tiles = co_tiles * ci_tiles * d->KH, total = tiles * kt;
   const int64_t nwg = pp_compute_units();
   if (total < nwg * 32) return 0;
-  int64_t best_r = 0, best_ls = 0, best_ns = 0;
-  double best_eff = 0.0;
-  for (int64_t r = 1; r <= 4; ++r) {
-    int64_t ns = r * nwg / tiles;
-    if (ns < 1) continue;
-    if (ns > kt / 32) ns = kt / 32;
-    if (ns < 1) continue;
-    const int64_t ls = ceil_div64(kt, ns);
-    ns = ceil_div64(kt, ls);
-    const double eff = (double)total / ((double)nwg * (double)(ceil_div64(ns * tiles, nwg) * ls));
-    if (eff > best_eff + 0.02 || best_r == 0) best_r = r, best_ls = ls, best_ns = ns, best_eff = eff;
-    if (best_eff >= 0.95) break;
-  }
-  if (best_r == 0 || best_eff < 0.80) return 0;
-  const int64_t items = best_ns * tiles;
+  const SlabPlan sp = slab_plan(kt, tiles, nwg);
+  if (sp.ns == 0 || sp.eff < 0.80) return 0;
+  const int64_t items = sp.ns * tiles;
   const int64_t rounds = ceil_div64(items, nwg);
   if (items * 128 * 384 >= (1ll << 31)) return 0;
-  if (L) *L = (int)best_ls;
-  if (slabs_out) *slabs_out = (int)best_ns;
+  if (L) *L = (int)sp.ls;
+  if (slabs_out) *slabs_out = (int)sp.ns;
   if (slab_floats) *slab_floats = (size_t)items * 128 * 384;
   return (int)ceil_div64(items, rounds);
 }
@@ -860,21 +810,9 @@ int mcdseg_internal_wgrad_pp3_launch(const mcdseg_conv_desc* d, int math, const 
   int L = 0, slabs = 0;
   const int nwg = mcdseg_internal_wgrad_pp3_plan(d, math, &L, nullptr, &slabs);
   MCD_REQUIRE(nwg > 0 && slabs > 0, "conv_wgrad_split_pp3: the geometry has no plan");
-  const int64_t xb = (int64_t)d->N * d->Cin * d->H * d->W * 2, yb = (int64_t)d->N * d->Cout * d->Ho * d->Wo * 2;
-  MCD_REQUIRE(xb + 4096 < (1ll << 31) && yb + 4096 < (1ll << 31) && (d->Ncb == 0 || d->Ncb >= d->N),
-              "conv_wgrad_split_pp3: pre-split operands need < 2 GiB per operand piece and Ncb >= N");
-  p.x_cb = x_cb; p.dy_cb = dy_cb; p.slab = slab;
-  p.N = d->N; p.Cin = d->Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.Ho = d->Ho; p.Wo = d->Wo;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.co_tiles = ceil_div(d->Cout, 128); p.ci_tiles = ceil_div(d->Cin, 128);
-  p.tiles_x = ceil_div(d->Wo, 16); p.tiles_y = d->Ho;
-  p.kt = d->N * p.tiles_x * p.tiles_y;
-  p.L = L; p.nwg = nwg;
-  p.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
-  p.slabs = slabs; p.items = slabs * p.co_tiles * p.ci_tiles * d->KH;
-  p.x_cb_bytes = (int)xb; p.dy_cb_bytes = (int)yb;
-  p.x_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cin * d->H * d->W * 2;  // (F16X1 reads piece 0 only)
-  p.dy_piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * d->Cout * d->Ho * d->Wo * 2;
+  if (const int e = fill_params(p, "conv_wgrad_split_pp3", d, math, x_cb, dy_cb, slab, 128, L, nwg, slabs)) return e;
+  const int tiles_all = p.co_tiles * p.ci_tiles * d->KH;
+  p.items = slabs * tiles_all;
   const dim3 grid((unsigned)(8 * ceil_div(nwg, 8)));
   if (math == MCDSEG_MATH_F16X1)
     hipLaunchKernelGGL(conv_wgrad_split_pp3_kernel<SplitF16x1>, grid, dim3(512), 0, st, p);
@@ -882,7 +820,7 @@ int mcdseg_internal_wgrad_pp3_launch(const mcdseg_conv_desc* d, int math, const 
     hipLaunchKernelGGL(conv_wgrad_split_pp3_kernel<SplitF16x3>, grid, dim3(512), 0, st, p);
   MCD_LAUNCH_CHECK("conv_wgrad_split_pp3");
   hipLaunchKernelGGL(wgrad_reduce_rt_kernel, dim3((unsigned)ceil_div(d->Cin, 64), (unsigned)d->Cout), dim3(256), 0, st, (const float*)slab, dw, d->Cout,
-                     d->Cin, d->KH, p.ci_tiles, slabs, p.co_tiles * p.ci_tiles * d->KH, x_bound, dy_bound);
+                     d->Cin, d->KH, p.ci_tiles, slabs, tiles_all, x_bound, dy_bound);
   MCD_LAUNCH_CHECK("wgrad_reduce_rt");
   return 0;
 }

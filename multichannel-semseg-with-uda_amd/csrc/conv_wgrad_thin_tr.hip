@@ -35,8 +35,6 @@ struct ThinTrParams {
   int uxp;          // window units per piece, padded to whole DMA slots
 };
 
-typedef short tt_s16x4 __attribute__((ext_vector_type(4)));
-typedef short tt_s16x8 __attribute__((ext_vector_type(8)));
 
 template <int CIN8, int MT, int NTL, int TR>
 __global__ __launch_bounds__(256) void conv_wgrad_thin_tr_kernel(ThinTrParams p) {
@@ -105,19 +103,8 @@ __global__ __launch_bounds__(256) void conv_wgrad_thin_tr_kernel(ThinTrParams p)
 #pragma unroll
     for (int j = 0; j < NTL; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  auto tr_read = [&](int addr) -> tt_s16x4 {
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) tt_s16x4*)(tt_smem + addr));
-#else
-    (void)addr;
-    return tt_s16x4{};
-#endif
-  };
   auto frag_at = [&](int addr, int step) -> f16x8 {  // two 4-pixel blocks `step` bytes apart -> 8 consecutive k
-    const tt_s16x4 lo = tr_read(addr);
-    const tt_s16x4 hi = tr_read(addr + step);
-    const tt_s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(f16x8, v);
+    return mcd_frag_pack<f16x8>(mcd_tr_read(tt_smem + addr), mcd_tr_read(tt_smem + addr + step));
   };
 
   const int per_img = p.tiles_x * p.tiles_y;

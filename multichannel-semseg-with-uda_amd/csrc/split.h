@@ -1,4 +1,5 @@
-// Operand-split policies of the matrix-pipe convolutions (conv_gemm_split.hip, conv_wgrad_split.hip, bn.hip).
+// Operand-split policies of the matrix-pipe convolutions (conv_gemm_split.hip, conv_wgrad_split.hip, bn.hip), and at the end of the file
+// what their weight-gradient kernels share: the transposing LDS reads, the companion-piece descriptor, the piece stride, the CU count.
 //
 // gfx950 has no fp32-grade matrix instruction faster than the vector rate (no xf32/TF32), so an fp32 product a*b is
 // carried through the 16-bit MFMA pipe as a sum of exact piece products:
@@ -125,3 +126,76 @@ static inline int mcd_math_pieces(int math) { return (math == 3 || math == 1) ? 
 // the arithmetic whose STORAGE (companions, weight images, bounds) a math shares: F16X1 multiplies F16X3's operands
 static inline int mcd_storage_math(int math) { return math == 1 ? 3 : math; }
 static inline bool mcd_math_known(int math) { return math == 1 || math == 3 || math == 6; }
+
+// ---- transposing LDS reads (ds_read_b64_tr_b16): the MFMA fragments of the weight-gradient kernels whose operands sit in LDS as in
+// memory, 16-byte units of 8 channels x 1 pixel (conv_wgrad_split.hip, conv_wgrad_split_pp.hip) ----------------------------------
+typedef short mcd_s16x4 __attribute__((ext_vector_type(4)));
+typedef short mcd_s16x8 __attribute__((ext_vector_type(8)));
+
+// the LDS byte address of (a place in) a __shared__ array: what a ds_ instruction written as inline assembly takes
+__device__ __forceinline__ unsigned mcd_lds_addr(const void* shared) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)shared;
+#else
+  (void)shared;
+  return 0;
+#endif
+}
+
+// One transposing read at base + OFF (a compile-time offset).  Inline assembly: for a compiler-visible LDS load the wait-count pass
+// puts an s_waitcnt vmcnt(0) in front whenever an LDS-DMA may be pending (it cannot tell that the DMA targets another stage), which
+// would drain the prefetch at the head of every read phase.  The read completes at the lgkmcnt(0) of the wait that closes the
+// caller's read phase; the caller then re-defines the registers behind that wait (`settle`: asm volatile("" : "+v"(f))) so that no
+// matrix instruction can be scheduled ahead of it.
+template <int OFF>
+__device__ __forceinline__ mcd_s16x4 mcd_tr_read_at(unsigned base) {
+  mcd_s16x4 v;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(base), "n"(OFF) : "memory");
+#else
+  (void)base;
+  v = mcd_s16x4{};
+#endif
+  return v;
+}
+
+// The same read through the builtin, for the kernels whose reads the compiler may see (no LDS-DMA the wait-count pass knows of is
+// pending when they read: conv_wgrad_split_tr64_kernel hides its DMAs, conv_wgrad_thin_tr.hip has drained them).
+__device__ __forceinline__ mcd_s16x4 mcd_tr_read(const unsigned char* lds) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) mcd_s16x4*)(lds));
+#else
+  (void)lds;
+  return mcd_s16x4{};
+#endif
+}
+
+// two 4-pixel reads -> the 8 k slots of a fragment: 0-3 from the lane's first quad, 4-7 from its second
+template <class F>
+__device__ __forceinline__ F mcd_frag_pack(mcd_s16x4 lo, mcd_s16x4 hi) {
+  const mcd_s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  return __builtin_bit_cast(F, v);
+}
+template <class F, int LO, int HI>
+__device__ __forceinline__ F mcd_tr_frag(unsigned base) {
+  const mcd_s16x4 lo = mcd_tr_read_at<LO>(base);
+  const mcd_s16x4 hi = mcd_tr_read_at<HI>(base);
+  return mcd_frag_pack<F>(lo, hi);
+}
+
+// The buffer descriptor a wave stages companion pieces through: `bytes` of the companion `cb` from byte `first` on (a whole piece, or
+// several with the stride between them).  It starts `bias` = mcd_piece_bias(pad) bytes below that so that the SGPR offset (tile + tap
+// shift, + bias) is never negative; the launchers admit a kernel only while what one descriptor covers stays below 2 GiB.
+__device__ __forceinline__ int mcd_piece_bias(int pad) { return pad * 16 + 16; }
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t mcd_piece_rsrc(const void* cb, long long first, int bytes, int bias) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)cb + first - bias), 0, bytes + bias, 0x00020000);
+}
+
+// bytes between the pieces of a companion of `per_image` 16-bit values per image: the companions' own batch (mcdseg_conv_desc.Ncb) apart;
+// 0 for F16X1, which reads piece 0 only
+static inline long long mcd_piece_stride(const mcdseg_conv_desc* d, int math, long long per_image) {
+  return math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * per_image * 2;
+}
+
+// CUs of the current device (256, the MI355X's, where the query fails): defined in conv_gemm_split_pp.hip
+int mcdseg_internal_device_cus();
