@@ -385,6 +385,40 @@ int mcdseg_predict_labels(const float* z1, const float* z2, uint8_t* labels, flo
 size_t mcdseg_predict_up8_workspace_bytes(int32_t N, int32_t Hi);
 int mcdseg_predict_labels_up8(const float* s, const float* w, uint8_t* labels, float* entropy, int32_t N, int32_t C, int32_t C_used,
                               int32_t Hi, int32_t Wi, void* workspace, size_t workspace_bytes, void* stream);
+/* The Monte-Carlo dropout loss of the uncertain source-only model, all T draws in one pass over the pixels
+ * (UncertainDRNSeg.get_loss, models/dilated_fcn.py:169-214; forward :153-161; source_uncertain_trainer.py:136-140).
+ * The reference runs the network T = n_dropout_exp times; its only randomness is Dropout2d(0.2) on the scores s [N,C,Hi,Wi] -- a
+ * factor m_t[n,c] in {0, keep_scale} -- and one scalar r_t = np.random.rand() per draw, and both up-samplers are depthwise and linear:
+ * with U = up8(s, w_up), V = up8(s, w_std) (mcdseg_up8_fwd's values), pred_mean_t = m_t U, pred_std_t = m_t relu(V),
+ * y_hat_t = m_t U + (m_t relu(V)) r_t.  Per pixel i of sample n with label g, W = sum_i class_weight[g_i] (or *wsum_in), HW = 64 Hi Wi,
+ * p_t = softmax(y_hat_t)[g], S = sum_t p_t:
+ *   losses[0]        = B   = (1/T) sum_t CrossEntropyLoss2d(m_t U, g)     (loss.py:7-13; dilated_fcn.py:178, 202)
+ *   losses[1]        = W
+ *   losses[2 .. 2+N) = U_n = (lambda/HW) sum_i log(S_i / T)               (dilated_fcn.py:183-204, 212; the reference's sign: + log)
+ * keep: uint8 [T,N,C], 1 = the channel is kept in that draw (m = keep_scale = 1/(1-p), 1.25 for the reference's p = 0.2), 0 = dropped;
+ * r: fp32 [T] on the device.  Pixels whose label is ignore_index or outside [0,C) contribute 0 to B, W, U_n and to every gradient; HW
+ * stays the full pixel count.  class_weight may be NULL (weights 1).  C <= 48, 1 <= T <= 32 and N <= 65535 (argument errors otherwise).
+ * Softmax and log-sum-exp subtract the maximum (the reference's bare log(sum(exp)) is the same value wherever it is finite).
+ * mcdseg_up8_uncertain_loss_bwd: the gradients w.r.t. U and V (never stored themselves) for the upstream gradients gb (of B, device
+ * scalar) and gu [N] (of U_n), read from device memory -- nothing synchronises with the host:
+ *   GU[c] = sum_t m_t[c] (a_t[c] + b_t[c]),   GV[c] = sum_t m_t[c] [V[c] > 0] r_t b_t[c]          (both [N,C,8Hi,8Wi])
+ *   a_t[c] = gb cw[g] / (T W) (softmax(m_t U)[c] - [c = g]),   b_t[c] = gu[n] (lambda/HW) (p_t / S) ([c = g] - softmax(y_hat_t)[c])
+ * wsum: the forward's losses + 1.  mcdseg_up8_bwd(GU, w_up, s, ...) and mcdseg_up8_bwd(GV, w_std, s, ...) finish the backward pass.
+ * No tensor with a T dimension is formed; loss values are summed per workgroup and then in fp64 (no atomics: bit-reproducible). */
+size_t mcdseg_up8_uncertain_loss_workspace_bytes(int32_t N, int32_t Hi, int32_t Wi);
+int mcdseg_up8_uncertain_loss_fwd(const float* s, const float* w_up, const float* w_std, const int64_t* labels,
+                                  const float* class_weight, int64_t ignore_index, const uint8_t* keep, const float* r,
+                                  float keep_scale, const float* wsum_in, float lambda, float* losses, int32_t N, int32_t C,
+                                  int32_t Hi, int32_t Wi, int32_t T, void* workspace, size_t workspace_bytes, void* stream);
+int mcdseg_up8_uncertain_loss_bwd(const float* s, const float* w_up, const float* w_std, const int64_t* labels,
+                                  const float* class_weight, int64_t ignore_index, const uint8_t* keep, const float* r,
+                                  float keep_scale, const float* wsum, float lambda, const float* gb, const float* gu, float* GU,
+                                  float* GV, int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t T, void* stream);
+/* The uncertain tester's map (source_uncertain_tester.py:158-166 with the channel sum that its line 163 and dilated_fcn.py:160 leave
+ * commented out; plt.imshow takes the literal [C,H,W] array only for C = 3 or 4):
+ * out[n,y,x] = sum_{c < C_used} relu(up8(s, w_std))[n,c,y,x], fp32 [N,8Hi,8Wi], without the C-channel full-resolution tensor. */
+int mcdseg_up8_std_sum(const float* s, const float* w_std, float* out, int32_t N, int32_t C, int32_t C_used, int32_t Hi, int32_t Wi,
+                       void* stream);
 /* Depth image of the multitask tester (adapt_multitask_tester.py:148-155 with transform.py:285-294, unnormalize): d [N,Cd,Hi,Wi] fp32
  * (Cd = 1 or 3, the depth head) -> img [N,8Hi,8Wi,3] uint8 HWC.  v = bilinear x8 of d (mcdseg_bilinear8_fwd's fp32 values) in channel
  * Cd == 1 ? 0 : k; t = ((double)v * STD[k] + MEAN[k]) * 255 with every operation rounded in double (numpy's promotion against the

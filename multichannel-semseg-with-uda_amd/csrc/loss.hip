@@ -49,15 +49,9 @@ __global__ __launch_bounds__(256) void wsum_finalize_kernel(const float* __restr
 // are cut into groups by branches on an opaque, always-true scalar: basic-block boundaries are the only fence the instruction
 // scheduler respects here, and without them it interleaves the exponential chains of all classes (about seven registers
 // each) and spills hundreds of registers.
-#define MCD_OPAQUE_TRUE(name) \
-  int name = 1;               \
-  asm volatile("" : "+s"(name))
-
-// exp of a NON-POSITIVE argument (a logit minus the pixel's maximum): v_exp_f32(x log2 e), two instructions where expf spends fifteen on
-// a range reduction and a scaling that such an argument never needs (round 6: the fused loss kernel evaluates 82 of these per pixel and
-// was bound by them after round 5's wait fix).  Relative error: the instruction's 1 ulp plus |x| 2^-24 from rounding x log2 e -- below
-// 2e-7 for every class that carries probability (x > -3); exp(-inf) = 0 for the padding classes; results below 2^-126 flush to zero.
-__device__ __forceinline__ float exp_nonpos(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
+// (MCD_OPAQUE_TRUE, exp_nonpos and the patch constants UP_COLS / UP_JP / UP_NT live in up8_patch.h, with the staging fragments of the
+// register-staged up-sampling front end, which csrc/uncertain.hip uses as well)
+#include "up8_patch.h"
 
 template <int NCMAX, bool TWO>
 __device__ __forceinline__ void pixel_losses(float (&a)[NCMAX], float (&b)[NCMAX], int y, float wy, float ce_coef, float diff_coef,
@@ -267,7 +261,7 @@ __device__ __forceinline__ void pixel_dist(float (&a)[NCMAX], float (&b)[NCMAX],
 // kernel rows (k, k+8).  The multiply-adds run in the order of up8_fwd_kernel (absent inputs staged as zeros), so logits,
 // the losses' summands and the gradients equal the two-pass result bit for bit; only the summation order of the loss
 // values differs (per lane over its items, then the block, then fp64 over blocks).
-constexpr int UP_COLS = 64, UP_JP = 9, UP_NT = 512;  // UP_JP: input-column pairs (ix-1, ix) a 64-pixel row segment touches
+// (UP_COLS = 64, UP_JP = 9 input-column pairs a 64-pixel row segment touches, UP_NT = 512: up8_patch.h)
 
 // ---- the same kernel with nothing between an item's stores and the next item's inputs ----------------------------------------
 // The kernel above fetches the next item's scores into registers (and reads labels and class weights from memory inside the item):

@@ -77,45 +77,18 @@ __global__ __launch_bounds__(UP_NT) void MCD_FRONT_UP8(const float* __restrict__
   const int nseg = (Wo + UP_COLS - 1) / UP_COLS;
   const int items = N * (Hi + 1) * nseg;
   const int ky0 = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  for (int i = threadIdx.x; i < HEADS * NCMAX * 256; i += UP_NT) {
-    const int b = i & 1, a = (i >> 1) & 1, kx = (i >> 2) & 7, ky = (i >> 5) & 7, hc = i >> 8;
-    const int c = hc % NCMAX;
-    // classes past C: taps (1, 0, 0, 0) against scores (-inf, 0, 0, 0) below give the logit -inf with no test in the pixel loop
-    wl[i] = c < C ? (hc >= NCMAX ? w2 : w1)[c * 256 + (ky + 8 * a) * 16 + kx + 8 * b] : ((a | b) == 0 ? 1.f : 0.f);
-  }
+  MCD_UP8_STAGE_TAPS  // (csrc/up8_patch.h, as the other MCD_UP8_ fragments of this kernel)
   constexpr int nstage = HEADS * NCMAX * UP_JP * 4;
   float sreg[SREG];
   auto fetch = [&](int item) {  // scores of one item -> registers (zeros outside the map)
-    const int seg = item % nseg, r = item / nseg;
-    const int iyg = r % (Hi + 1), n = r / (Hi + 1);
-    const int ixb = seg * (UP_COLS / 8) - 1;
-#pragma unroll
-    for (int k = 0; k < SREG; ++k) {
-      const int i = threadIdx.x + k * UP_NT;
-      float v = 0.f;
-      if (i < nstage) {
-        const int b = i & 1, a = (i >> 1) & 1, q = i >> 2;
-        const int j = q % UP_JP, hc = q / UP_JP;
-        const int c = hc % NCMAX;
-        const int iy = iyg - a, ix = ixb + j + 1 - b;
-        if (c >= C)
-          v = (a | b) == 0 ? -INFINITY : 0.f;
-        else if (iy >= 0 && iy < Hi && ix >= 0 && ix < Wi)
-          v = (hc >= NCMAX ? s2 : s1)[(((size_t)n * C + c) * Hi + iy) * Wi + ix];
-      }
-      sreg[k] = v;
-    }
+    MCD_UP8_FETCH(item)
   };
   float ce1 = 0.f, ce2 = 0.f, dsum = 0.f;
   int item = blockIdx.x;
   if (item < items) fetch(item);
   for (; item < items; item += gridDim.x) {
     __syncthreads();  // the previous item's readers are done (and, first time round, the kernels are staged)
-#pragma unroll
-    for (int k = 0; k < SREG; ++k) {
-      const int i = threadIdx.x + k * UP_NT;
-      if (i < nstage) sin[i] = sreg[k];
-    }
+    MCD_UP8_COMMIT
     __syncthreads();
     if (item + (int)gridDim.x < items) fetch(item + gridDim.x);
     const int seg = item % nseg, r = item / nseg;
@@ -134,31 +107,7 @@ __global__ __launch_bounds__(UP_NT) void MCD_FRONT_UP8(const float* __restrict__
       int woff = (ky0 * 8 + kx0) * 4, soff = jp * 4;
       asm volatile("" : "+v"(woff), "+v"(soff));
       float a[NCMAX], b[NCMAX];
-#pragma unroll
-      for (int c0 = 0; c0 < NCMAX; c0 += 4) {
-        MCD_OPAQUE_TRUE(go);  // groups of four classes in basic blocks of their own (see pixel_losses)
-        if (go) {
-#pragma unroll
-          for (int c = c0; c < c0 + 4; ++c) {
-            if (c >= NCMAX) continue;
-            b[c] = -INFINITY;
-#pragma unroll
-            for (int h = 0; h < HEADS; ++h) {
-              const float4 wv = *reinterpret_cast<const float4*>(wl + woff + (h * NCMAX + c) * 256);
-              const float4 sv = *reinterpret_cast<const float4*>(sin + soff + (h * NCMAX + c) * (UP_JP * 4));
-              float o = 0.f;
-              o = fmaf(sv.x, wv.x, o);
-              o = fmaf(sv.y, wv.y, o);
-              o = fmaf(sv.z, wv.z, o);
-              o = fmaf(sv.w, wv.w, o);
-              if (h == 0)
-                a[c] = o;
-              else
-                b[c] = o;
-            }
-          }
-        }
-      }
+      MCD_UP8_LOGITS(a, b)
       const size_t HW = (size_t)Ho * Wo;
       const size_t hw = (size_t)oy * Wo + ox;
       int y = -1;

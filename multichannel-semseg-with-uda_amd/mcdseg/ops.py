@@ -11,6 +11,8 @@ mirror the ATen call sites of the reference's hot path:
   diff2d           mean |softmax - softmax|                         loss.py:93-100
   mcd_losses       both of the above in one fused kernel            adapt_trainer.py:163-212
   prob_distance    the other distances of --d_loss (jsd, symkl, ...) loss.py:66-189
+  up8_uncertain_loss  the T Monte-Carlo dropout passes of UncertainDRNSeg.get_loss in one kernel   models/dilated_fcn.py:169-214
+  up8_std_sum      the uncertain tester's map, sum_c relu(up_std(s))   source_uncertain_tester.py:158-166
 """
 import collections
 import contextlib
@@ -2151,6 +2153,89 @@ def up8_mcd_losses(s1, w1, s2, w2, labels, class_weight, ignore_index=-100, ce_c
 def up8_backward(g, s, w, want_input, want_weight):
     """(d/ds, d/dw) of the up-sampler for the logit gradient ``g`` (either may be skipped)."""
     return _up8_bwd(g, w, s, want_input, want_weight)
+
+
+# ------------------------------------------------------------------------------------------------ Monte-Carlo dropout loss (uncertain model)
+def _check_draws(keep, r, n, c):
+    keep, r = _req(keep, "dropout keep mask", torch.uint8), _req(r, "dropout draw scalars r")
+    if keep.dim() != 3 or tuple(keep.shape[1:]) != (n, c) or tuple(r.shape) != (keep.shape[0],):
+        raise ValueError("mcdseg: keep must be uint8 [T,N,C] = [T,%d,%d] and r fp32 [T], got %s / %s" % (n, c, tuple(keep.shape), tuple(r.shape)))
+    return keep, r
+
+
+class _Up8UncertainLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, s, w_up, w_std, labels, class_weight, keep, r, keep_scale, lam, ignore_index, wsum):
+        L = lib()
+        s, w_up, w_std = _req(s, "scores"), _req(w_up, "up8 weight"), _req(w_std, "up8 weight (std)")
+        _check_up(s, w_up), _check_up(s, w_std)
+        n, c, hi, wi = s.shape
+        labels = _req(labels, "labels", torch.int64)
+        if tuple(labels.shape) != (n, 8 * hi, 8 * wi):
+            raise ValueError("mcdseg: labels must be [N,H,W] = %s, got %s" % ((n, 8 * hi, 8 * wi), tuple(labels.shape)))
+        class_weight = _req(class_weight, "class weights")
+        if class_weight is not None and class_weight.numel() != c:
+            raise ValueError("mcdseg: class weight has %d entries for %d classes" % (class_weight.numel(), c))
+        keep, r = _check_draws(keep, r, n, c)
+        t = keep.shape[0]
+        if wsum is None:
+            wsum = ce_normaliser(labels, class_weight, c, ignore_index)
+        wsum = _req(wsum, "CE normaliser")
+        losses = torch.empty(2 + n, dtype=torch.float32, device=s.device)
+        ws = _ws(L.mcdseg_up8_uncertain_loss_workspace_bytes(n, hi, wi), s.device)
+        with _timed("up8_uncertain_kernel<%s, false>" % uncertain_kernel_classes(c), (0, 8 * n * c * hi * wi + 8 * n * hi * wi * 64)):
+            check(L.mcdseg_up8_uncertain_loss_fwd(_p(s), _p(w_up), _p(w_std), _p(labels), _p(class_weight), int(ignore_index), _p(keep), _p(r),
+                                                  float(keep_scale), _p(wsum), float(lam), _p(losses), n, c, hi, wi, t, _p(ws),
+                                                  ctypes.c_size_t(ws.numel() * 4), _stream()), "up8_uncertain_loss_fwd")
+        ctx.save_for_backward(s, w_up, w_std, labels, class_weight, keep, r, losses)
+        ctx.consts = (float(keep_scale), float(lam), int(ignore_index))
+        return losses[0].clone(), losses[2:].clone()
+
+    @staticmethod
+    def backward(ctx, gb, gu):
+        s, w_up, w_std, labels, class_weight, keep, r, losses = ctx.saved_tensors
+        keep_scale, lam, ignore_index = ctx.consts
+        n, c, hi, wi = s.shape
+        gb, gu = _req(gb.reshape(1), "grad_output"), _req(gu.reshape(n), "grad_output")
+        g_u = torch.empty((n, c, 8 * hi, 8 * wi), dtype=torch.float32, device=s.device)
+        g_v = torch.empty_like(g_u)
+        with _timed("up8_uncertain_kernel<%s, true>" % uncertain_kernel_classes(c), (0, 8 * n * c * hi * wi * 65 + 8 * n * hi * wi * 64)):
+            check(lib().mcdseg_up8_uncertain_loss_bwd(_p(s), _p(w_up), _p(w_std), _p(labels), _p(class_weight), ignore_index, _p(keep), _p(r),
+                                                      keep_scale, _p(losses[1:]), lam, _p(gb), _p(gu), _p(g_u), _p(g_v), n, c, hi, wi,
+                                                      keep.shape[0], _stream()), "up8_uncertain_loss_bwd")
+        need = ctx.needs_input_grad
+        ds, dw_up = _up8_bwd(g_u, w_up, s, need[0], need[1])
+        del g_u
+        ds2, dw_std = _up8_bwd(g_v, w_std, s, need[0], need[2])
+        if ds is not None:
+            ds.add_(ds2)
+        return (ds, dw_up, dw_std) + (None,) * 8
+
+
+def uncertain_kernel_classes(c):
+    """the class count of the instantiation of ``up8_uncertain_kernel`` that serves ``c`` classes (csrc/uncertain.hip: unc_ncmax)"""
+    return 16 if c <= 16 else (24 if c <= 24 else (41 if c == 41 else 48))
+
+
+def up8_uncertain_loss(s, w_up, w_std, labels, class_weight, keep, r, uncertain_weight=0.1, ignore_index=-100, wsum=None, keep_scale=1.25):
+    """``UncertainDRNSeg.get_loss`` (models/dilated_fcn.py:169-214) behind the trunk, all T dropout draws in one pass: returns
+    ``(base_loss, uncertain_loss[N])`` -- the mean over the draws of CrossEntropyLoss2d(m_t up(s)) and, per sample,
+    uncertain_weight * mean_i log((1/T) sum_t softmax(m_t up(s) + m_t relu(up_std(s)) r_t)[label]) -- differentiable w.r.t.
+    ``s``, ``w_up`` and ``w_std``.  ``keep``: uint8 [T,N,C], 1 where Dropout2d kept channel c of sample n in draw t (factor
+    ``keep_scale`` = 1/(1-p), else 0); ``r``: fp32 [T], the reference's ``np.random.rand()`` per draw.  include/mcdseg.h has the formulas."""
+    return _Up8UncertainLoss.apply(s, w_up, w_std, labels, class_weight, keep, r, keep_scale, uncertain_weight, ignore_index, wsum)
+
+
+def up8_std_sum(s, w_std, n_used=None):
+    """``relu(up8(s, w_std))[:, :n_used].sum(1)`` as fp32 [N,8Hi,8Wi] without the C-channel full-resolution tensor: the aleatoric
+    uncertainty map of source_uncertain_tester.py:158-166"""
+    s, w_std = _req(s, "scores"), _req(w_std, "up8 weight (std)")
+    _check_up(s, w_std)
+    n, c, hi, wi = s.shape
+    n_used = c if n_used is None else int(n_used)
+    out = torch.empty((n, 8 * hi, 8 * wi), dtype=torch.float32, device=s.device)
+    check(lib().mcdseg_up8_std_sum(_p(s), _p(w_std), _p(out), n, c, n_used, hi, wi, _stream()), "up8_std_sum")
+    return out
 
 
 def predict_labels(z1, z2=None, n_used=None):

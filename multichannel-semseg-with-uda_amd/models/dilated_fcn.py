@@ -1,6 +1,7 @@
 """Segmentation wrappers around the DRN trunk (reference: models/dilated_fcn.py).
 
   DRNSeg                              :68-110   trunk + seg + up (source-only training, cfg1)
+  UncertainDRNSeg                     :113-214  DRNSeg + ``up_std`` and the Monte-Carlo dropout loss, all draws in one kernel
   DRNSegBase                = G       :217-250  trunk + 1x1 ``seg`` (ver1) / trunk only (ver2)
   DRNSegPixelClassifier     = F1/F2   :340-366  learned x8 depthwise transposed-conv up-sampler
   FusionDRNSegPixelClassifier         :431-470  fuse features, one up-sampler
@@ -14,7 +15,9 @@ State-dict keys follow the reference: ``base.<stage>...``
 ``up.weight`` / ``up1.weight`` / ``up2.weight``.
 """
 import math
+import os
 
+import numpy as np
 import torch
 import torch.nn as nn
 from torch.nn import Parameter
@@ -104,6 +107,118 @@ class DRNSeg(nn.Module):
     def optim_parameters(self, memo=None):
         yield from self.base.parameters()
         yield from self.seg.parameters()
+
+
+def fused_uncertain():
+    """MCDSEG_FUSED_UNCERTAIN=0 (host-side, read at every call): ``UncertainDRNSeg.get_loss`` runs the literal form -- T dropout
+    passes through both up-samplers and torch ops -- instead of the one-pass kernel; the parity test's other side and the timing baseline"""
+    return os.environ.get("MCDSEG_FUSED_UNCERTAIN", "1") != "0"
+
+
+class UncertainDRNSeg(nn.Module):
+    """DRNSeg with a second learned up-sampler ``up_std`` for the per-class aleatoric standard deviation and a Monte-Carlo dropout
+    loss (models/dilated_fcn.py:113-214).  State-dict keys are the reference's: ``base.*``, ``seg.{weight,bias}``, ``up.weight``,
+    ``up_std.weight`` (``dropout`` and ``criterion`` hold no parameters; the criterion's class weights are a buffer,
+    ``criterion.nll_loss.weight``, exactly as there).
+
+    ``get_loss`` does NOT run the network ``n_dropout_exp`` times as the reference does (:176-200).  Dropout2d acts on the scores
+    behind the trunk and both up-samplers are linear and depthwise, so up(m_t s) = m_t up(s): the trunk (train-mode BatchNorm, no
+    randomness of its own) yields the same scores in every pass.  One trunk pass under ``ops.bn_running_updates(T)`` -- the running
+    statistics move as in T passes -- and ``ops.up8_uncertain_loss`` over all T draws give the reference's losses and, through one
+    trunk backward, its gradients (DESIGN.md has the derivation and the fp64 check against the reference).
+
+    The draws: ``keep`` [T,N,C] from torch's generator on the device (Bernoulli(1 - p) per sample and channel, what Dropout2d draws)
+    and ``r`` [T] from a ``numpy.random.RandomState`` the module owns (``seed_draws``; the reference takes ``np.random.rand()``
+    from numpy's global state), uploaded without a synchronisation.  Both can be passed in.  A ``dropout`` module left in eval mode
+    (``--no_dropout``, ``fix_dropout_when_training``) keeps every channel with factor 1."""
+
+    def __init__(self, model_name, n_class, input_ch=3, pretrained_model=None, pretrained=True, use_torch_up=False, criterion=None,
+                 n_dropout_exp=10, uncertain_weight=0.1):
+        super().__init__()
+        self.base, out_dim = _trunk(model_name, pretrained, input_ch)
+        if pretrained_model is not None:
+            self.base.load_state_dict({k.replace("module.", ""): v for k, v in pretrained_model.items()}, strict=False)
+        self.seg = _seg_head(out_dim, n_class)
+        self.dropout = nn.Dropout2d(0.2)
+        self.criterion = criterion
+        self.n_dropout_exp = n_dropout_exp
+        self.uncertain_weight = uncertain_weight
+        self.up = _up(n_class, n_class, use_torch_up)
+        self.up_std = _up(n_class, n_class, use_torch_up)
+        self._draws = np.random.RandomState(int(torch.initial_seed()) % (2 ** 32))
+
+    def seed_draws(self, seed):
+        """reseed the stream the per-draw scalars r_t come from (the trainer: from ``--seed``)"""
+        self._draws = np.random.RandomState(int(seed) % (2 ** 32))
+
+    def forward(self, x):
+        x = self.dropout(self.seg(self.base(x)))
+        return ops.up8(x, self.up.weight), torch.relu(ops.up8(x, self.up_std.weight))  # (std must not be negative, :158)
+
+    def optim_parameters(self, memo=None):
+        yield from self.base.parameters()
+        yield from self.seg.parameters()
+
+    def _class_weight(self, device):
+        w = getattr(self.criterion, "weight", None)
+        return None if w is None else w.to(device=device, dtype=torch.float32)
+
+    def draw(self, n, c, device):
+        """(keep uint8 [T,N,C], r fp32 [T], keep_scale) of one step"""
+        t, p = self.n_dropout_exp, self.dropout.p
+        if self.dropout.training and p > 0.0:
+            keep = (torch.rand((t, n, c), device=device) >= p).to(torch.uint8)
+            scale = 1.0 / (1.0 - p)
+        else:
+            keep, scale = torch.ones((t, n, c), dtype=torch.uint8, device=device), 1.0
+        r = torch.from_numpy(self._draws.random_sample(t).astype(np.float32))
+        return keep, (r.pin_memory() if device.type == "cuda" else r).to(device, non_blocking=True), scale
+
+    def get_loss(self, x, gt, separately_returning=False, keep=None, r=None):
+        if not self.training:
+            self.train()  # as the reference's get_loss does (:172); a model in train mode keeps what --no_dropout / --fix_bn fixed
+        dropping = self.dropout.training
+        n, c, t = gt.size(0), self.seg.out_channels, self.n_dropout_exp
+        if keep is None or r is None:
+            k0, r0, scale = self.draw(n, c, x.device)
+            keep, r = (k0 if keep is None else keep), (r0 if r is None else r)
+        else:
+            scale = 1.0 / (1.0 - self.dropout.p) if dropping else 1.0
+        ignore = getattr(self.criterion, "ignore_index", -100)
+        weight = self._class_weight(x.device)
+        if fused_uncertain():
+            with ops.bn_running_updates(t):  # the running statistics and num_batches_tracked move as in T passes
+                s = self.seg(self.base(x))
+            base_loss, uncertain = ops.up8_uncertain_loss(s, self.up.weight, self.up_std.weight, gt, weight, keep, r, self.uncertain_weight,
+                                                          ignore, keep_scale=scale)
+        else:
+            base_loss, uncertain = self._literal_loss(x, gt, weight, ignore, keep, r, scale)
+        if separately_returning:
+            return base_loss, uncertain
+        return base_loss + uncertain
+
+    def _literal_loss(self, x, gt, weight, ignore, keep, r, scale):
+        """the reference's loop as written (:176-204): T passes of the whole network, the dropout factors applied to the scores,
+        both full-resolution maps of every draw, torch ops for the rest.  Labels outside [0, C) (which the reference's gather cannot
+        take) contribute nothing, as in the kernel."""
+        t = keep.shape[0]
+        n_pixel = gt.numel() / gt.size(0)
+        valid = (gt != ignore) & (gt >= 0) & (gt < self.seg.out_channels)
+        index = torch.where(valid, gt, torch.zeros_like(gt)).unsqueeze(1)
+        criterion = self.criterion if self.criterion is not None else (lambda z, g: ops.cross_entropy2d(z, g, None, ignore, True))
+        base_loss, prob_sum = 0, 0
+        for i in range(t):
+            m = keep[i].to(torch.float32).mul(scale)[:, :, None, None]
+            s = self.seg(self.base(x)) * m
+            mean = ops.up8(s, self.up.weight)
+            std = torch.relu(ops.up8(s, self.up_std.weight))
+            base_loss = base_loss + criterion(mean, gt)
+            noisy = mean + std * r[i]
+            log_partition = noisy.exp().sum(1).log()  # (bare, as the reference forms it; the kernel subtracts the maximum)
+            prob_sum = prob_sum + (torch.gather(noisy, 1, index).squeeze(1) - log_partition).exp()
+        base_loss = base_loss / t
+        log_mean = torch.where(valid, torch.log(prob_sum / t), torch.zeros_like(prob_sum))
+        return base_loss, log_mean.sum(1).sum(1) / n_pixel * self.uncertain_weight
 
 
 class DRNSegBase(nn.Module):

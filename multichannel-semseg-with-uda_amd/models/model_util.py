@@ -41,6 +41,18 @@ def get_full_model(net, res, n_class, input_ch, is_data_parallel=True):
     return _wrap(model, is_data_parallel)
 
 
+def get_full_uncertain_model(net, res, n_class, input_ch, criterion, is_data_parallel=True, n_dropout=10):
+    """models/model_util.py:42-54: ``UncertainDRNSeg`` (DRNSeg + ``up_std`` and the Monte-Carlo dropout loss)"""
+    if "drn" in net:
+        from models.dilated_fcn import UncertainDRNSeg
+        assert net in DRN_NAMES
+        model = UncertainDRNSeg(net, n_class, input_ch=input_ch, n_dropout_exp=n_dropout, criterion=criterion,
+                                pretrained=_pretrained_default())
+    else:
+        raise NotImplementedError("Only FCN, SegNet, PSPNet, DRNet, UNet are supported!")
+    return _wrap(model, is_data_parallel)
+
+
 def get_models(net_name, input_ch, n_class, res="50", method="MCD", is_data_parallel=False):
     if "drn" not in net_name or "fusenet" in net_name:
         raise NotImplementedError("Only FCN (Including Dilated FCN), SegNet, PSPNet UNet are supported!")
