@@ -28,10 +28,18 @@ _ALIGN = 64  # floats; keeps every view 256-byte aligned for the float4 kernels
 # parameter of a bucket has arrived the bucket's slice is reduced asynchronously (RCCL's own stream).  OFF by default: the five
 # 104 MB all-reduces of an MCD step are ~2 % of its time on xGMI; the switch exists so that a measured
 # scaling curve can be acted on without new code.  Results are those of the single all-reduce (sums of the same values).
-# The ORDER in which the buckets' collectives are started is the same on every rank whatever the ranks' timing: a bucket whose last
-# gradient has arrived is only "ready", and collectives are started strictly in bucket order (``_drain``) -- WHEN a gradient arrives
-# depends on rank-local state (a weight gradient left on the side stream arrives early through ``_early_grad``, one kept on the main
-# stream for lack of memory only at the end of the pass), WHETHER a bucket becomes ready in a pass depends on the graph alone.
+# The SEQUENCE of collectives is the same on every rank whatever the ranks' timing.  WHEN a gradient arrives depends on rank-local
+# state (a weight gradient left on the side stream arrives early through ``_early_grad``, one kept on the main stream for lack of memory
+# only at the end of the pass); the three things that decide which collectives a rank issues do not:
+#   * the order: a bucket whose last gradient has arrived is only "ready", and collectives are started strictly in bucket order
+#     (``_drain``);
+#   * WHETHER a bucket becomes ready in a pass: when every one of its parameters has arrived once, early or late, and whether or not
+#     the bucket has been spoilt meanwhile (``_arrive``) -- a spoilt bucket still takes its turn, with a collective nobody reads;
+#   * WHETHER a bucket is spoilt ("dirty": left to step()'s copy-and-reduce of the whole run, one more collective): when a parameter
+#     receives a second contribution in one pass (a weight used twice in the graph), a gradient on top of one that was there before the
+#     pass, or a second pass before step() -- counted from the reports ops makes per contribution, of which an early delivery and a
+#     "not through the sink" report are two spellings.  (Until both spellings counted alike, a rank that deferred both uses of a
+#     twice-used weight spoilt the bucket and a rank above the memory guard did not: one of them issued the fall-back all-reduce alone.)
 DP_OVERLAP = os.environ.get("MCDSEG_DP_OVERLAP", "0") == "1"
 DP_BUCKET_MB = float(os.environ.get("MCDSEG_DP_BUCKET_MB", "25"))
 
@@ -127,7 +135,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
             n = p.numel()
             if cur is None or cur["hi"] - o > limit:
                 cur = dict(lo=o, hi=o + n, ids=set(), arrived=0, work=None, dirty=False, early=set(), early_seen={}, ready=False,
-                           launched=False, unsunk=set(), events=[], index=len(fl["buckets"]))
+                           launched=False, unsunk=set(), seen=set(), events=[], index=len(fl["buckets"]))
                 fl["buckets"].append(cur)
             cur["lo"] = o
             cur["ids"].add(id(p))
@@ -146,25 +154,35 @@ class _FlatOptimizer(torch.optim.Optimizer):
         "first gradient of this parameter since the last step / zero_grad, nothing accumulated yet" leaves the bucket to step()'s
         copy-and-reduce path.  ``dw`` None: ops reports a contribution to this parameter's gradient that does NOT come through here
         (a second use of the weight in one graph, a weight gradient kept on the main stream) -- what ``p.grad`` will hold is then
-        more than an early copy, so an early copy of the same pass must not stand for it."""
+        more than an early copy, so an early copy of the same pass must not stand for it.  Every contribution is reported one way or
+        the other, which one is rank-local: the bucket is spoilt by the SECOND report for a parameter, and by a report that finds a
+        gradient from before the pass, whichever way the two came (module comment)."""
         fl = self._flat
         b = fl["bucket_of"].get(id(p)) if fl is not None else None
         if b is None:
             return
+        again = id(p) in b["seen"] or id(p) in b["unsunk"] or p.grad is not None
         if dw is None:
-            b["unsunk"].add(id(p))
-            if id(p) in b["early"]:
+            b["unsunk"].add(id(p))  # (arrives through its post-accumulate hook: ``_grad_arrived``)
+            if again:
                 self._spoil(b)
             return
-        if (b["ready"] or b["dirty"] or id(p) in b["early"] or id(p) in b["unsunk"] or p.grad is not None
-                or b["arrived"] >= len(b["ids"])):
+        if b["ready"] or b["dirty"] or again:
             self._spoil(b)
+        else:
+            fl["views"][id(p)][3].copy_(dw)
+            self._copied(b, dw)
+            b["early"].add(id(p))
+        self._arrive(b, p)
+
+    def _arrive(self, b, p):
+        """the parameter's first arrival in this pass, early or through its hook, copied or not: the bucket is ready -- takes its turn
+        in ``_drain`` -- once each of its parameters has arrived, spoilt or clean (on another rank it may be clean still)"""
+        if id(p) in b["seen"]:
             return
-        fl["views"][id(p)][3].copy_(dw)
-        self._copied(b, dw)
-        b["early"].add(id(p))
+        b["seen"].add(id(p))
         b["arrived"] += 1
-        if b["arrived"] == len(b["ids"]):
+        if b["arrived"] == len(b["ids"]) and not b["ready"]:
             b["ready"] = True
             self._drain()
 
@@ -231,20 +249,17 @@ class _FlatOptimizer(torch.optim.Optimizer):
         if (id(p) in b["early"] and not b["dirty"] and id(p) not in b["unsunk"] and b["early_seen"].get(id(p), 0) == 0):
             b["early_seen"][id(p)] = 1  # the gradient the side stream delivered (``_early_grad``) has now reached p.grad: nothing to do
             return
-        if b["ready"] or b["dirty"] or b["arrived"] >= len(b["ids"]) or id(p) in b["early"]:
+        if b["ready"] or b["dirty"] or id(p) in b["seen"]:
             # A SECOND backward pass before step() (MCDSolver's step B: two loss.backward() calls, then optimizer_f.step()): p.grad
             # now holds the accumulated local gradient, while the bucket's slice is being -- or has been -- summed over the ranks
             # from the first pass alone.  (Or: p.grad holds more than the early copy, ``unsunk``.)  Wait for the collective in flight
             # (the copy below must not race it), and leave the bucket to step()'s copy-and-reduce path, which reads the accumulated
             # p.grad of every parameter.
             self._spoil(b)
-            return
-        fl["views"][id(p)][3].copy_(p.grad)
-        self._copied(b, p.grad)
-        b["arrived"] += 1
-        if b["arrived"] == len(b["ids"]):
-            b["ready"] = True
-            self._drain()
+        else:
+            fl["views"][id(p)][3].copy_(p.grad)
+            self._copied(b, p.grad)
+        self._arrive(b, p)
 
     def _finish_overlap(self, ps):
         """waits for the collectives the hooks started; True when every gradient of ``ps`` has been reduced that way (else the
@@ -263,7 +278,7 @@ class _FlatOptimizer(torch.optim.Optimizer):
             if b["work"] is not None:  # (zero_grad() without step(): the reference's literal loop computes G's gradients in step B and
                 b["work"].wait()       # never applies them -- the next pass's copies must not race a collective still in flight)
             b["arrived"], b["work"], b["dirty"], b["ready"], b["launched"] = 0, None, False, False, False
-            b["early"].clear(), b["early_seen"].clear(), b["unsunk"].clear(), b["events"].clear()
+            b["early"].clear(), b["early_seen"].clear(), b["unsunk"].clear(), b["seen"].clear(), b["events"].clear()
         if self._flat is not None and "next" in self._flat:
             self._flat["next"] = 0
 

@@ -182,6 +182,79 @@ def test_flat_sgd_early_copy_does_not_stand_for_a_summed_gradient():
         optim.DP_OVERLAP, optim.mdist.is_distributed, FlatSGD._require_gpu, optim.mdist.all_reduce_sum_async = old
 
 
+@pytest.mark.parametrize("opt_name", ["FlatSGD", "FlatAdam"])
+def test_twice_used_weight_gives_both_ranks_one_sequence_of_collectives(opt_name, monkeypatch):
+    """A weight used twice in one backward graph (MultiTaskMCDSolver's step A) under MCDSEG_DP_OVERLAP=1, on two ranks in different
+    rank-local states: "rank A" has room to defer, both contributions come through ``_early_grad(p, dw)``; "rank B" is above the
+    memory guard, both are reported as ``_early_grad(p, None)`` and the summed ``p.grad`` arrives through the hook.  A once-used weight
+    sits in a second bucket.  What each rank then asks of the process group -- the bucket exchanges during the pass and, in step(),
+    the fall-back all-reduce of the run -- must be ONE sequence (a collective only one rank issues pairs with the other's next one, or
+    with nothing: wrong sums or a hang), and both updates must use the full summed gradient.  Single process, two optimizer instances,
+    the two entry points of ``mcdseg.dist`` replaced by recorders that sum "two ranks holding the same gradients": nothing can hang."""
+    from mcdseg import optim
+    cls = getattr(optim, opt_name)
+    monkeypatch.setattr(optim, "DP_OVERLAP", True)
+    monkeypatch.setattr(optim, "DP_BUCKET_MB", 0.0)      # every parameter a bucket of its own
+    monkeypatch.setattr(cls, "_require_gpu", False)
+    monkeypatch.setattr(optim.mdist, "is_distributed", lambda: True)
+    monkeypatch.setattr(optim.mdist, "world_size", lambda: 2)
+    log = []
+
+    class _Work:
+        def wait(self):
+            pass
+
+    def _async(flat):
+        log.append(("async", flat.numel()))
+        flat.mul_(2)
+        return _Work()
+
+    def _sync(flat):
+        log.append(("sync", flat.numel()))
+        return flat.mul_(2)
+
+    monkeypatch.setattr(optim.mdist, "all_reduce_sum_async", _async)
+    monkeypatch.setattr(optim.mdist, "all_reduce_sum_", _sync)
+    used = []
+
+    def _plain_update(p, g, *rest, **kw):
+        """p -= 0.1 * grad_scale * g in the place of either kernel; grad_scale is the last positional argument of both entries"""
+        gs = rest[-1]
+        used.append((g * gs).clone())
+        p.sub_(0.1 * gs * g)
+
+    monkeypatch.setattr(optim.ops, "sgd_momentum_flat_", _plain_update)
+    monkeypatch.setattr(optim.ops, "adam_flat_", _plain_update)
+    gen = torch.Generator().manual_seed(4)
+    dw1, dw2, gq = torch.randn(6, generator=gen), torch.randn(6, generator=gen), torch.randn(3, generator=gen)
+    seqs, after = {}, {}
+    for rank in ("A", "B"):
+        q, p = torch.nn.Parameter(torch.zeros(3)), torch.nn.Parameter(torch.zeros(6))   # q: used once; p: used twice
+        opt = cls([q, p], lr=0.1)
+        opt._ensure_flat()
+        bs = opt._flat["buckets"]
+        assert len(bs) == 2 and bs[0]["ids"] == {id(p)} and bs[1]["ids"] == {id(q)}
+        del log[:], used[:]
+        if rank == "A":
+            opt._early_grad(p, dw1.clone())
+            opt._early_grad(p, dw2.clone())
+        else:
+            opt._early_grad(p, None)
+            opt._early_grad(p, None)
+        p.grad = dw1 + dw2                      # what the ``_LateGrad`` node / the accumulation hands to AccumulateGrad at the end
+        opt._grad_arrived(p)
+        q.grad = gq.clone()
+        opt._grad_arrived(q)
+        opt.step()
+        seqs[rank], after[rank] = list(log), (p.detach().clone(), q.detach().clone())
+        assert len(used) == 1 and torch.equal(used[0][:3], gq) and torch.equal(used[0][64:70], dw1 + dw2), rank
+        assert all(not (b["dirty"] or b["ready"] or b["launched"] or b["arrived"] or b["unsunk"] or b["early"]) for b in bs)
+    print("rank A:", seqs["A"], " rank B:", seqs["B"])
+    assert seqs["A"] == seqs["B"], seqs
+    for rank in ("A", "B"):
+        assert torch.equal(after[rank][0], -0.1 * (dw1 + dw2)) and torch.equal(after[rank][1], -0.1 * gq), rank
+
+
 def test_single_process_helpers():
     from mcdseg import dist as mdist
     assert mdist.world_size() == 1 and mdist.rank() == 0 and not mdist.is_distributed()

@@ -384,6 +384,54 @@ def test_two_ranks_bucketed_overlap_with_rank_local_arrival_orders(tmp_path):
         assert out[1][k] == out[2][k], k
 
 
+def test_two_ranks_with_unequal_shards_take_the_global_step(tmp_path):
+    """The property the data-parallel path exists for, through the real kernels and a real process group: two ranks holding
+    DIFFERENT shards -- rank 0's labels about 90 % without weight -- take the step one process takes on the concatenated batch
+    (tests/dp_shard_worker.py: the product's two ver2 heads on a feature-map leaf, no BatchNorm between inputs and loss; once with
+    ``get_optimizer``'s SGD and once with its Adam, both in one launch per world).  World 1, world 2 and the fp64 torch statement of
+    that step (tests/dp_shard_ref.py): every head parameter's update and the feature gradient of each HIP run within the convolution
+    bar of test_conv_fprop_dgrad_wgrad, 2e-5 of the tensor's largest entry, of fp64.  A rank-local normaliser, an ignored ``wsum_in``
+    or a missing 1/world lies more than 100 bars away
+    (tests/test_dp_shard_ref_host.py::test_two_rank_head_step_separates_the_normalisers)."""
+    _need_gpu()
+    import numpy as np
+    import dp_shard_ref as ref
+    here = os.path.dirname(os.path.abspath(__file__))
+    worker = os.path.join(here, "dp_shard_worker.py")
+    feats, y, cw, heads = ref.head_problem()
+    hc = ref.HEAD_CASE
+    ce = [float(ref.global_ce(z, y, cw, hc["ignore_index"])[0]) for z in ref.head_logits(feats, heads)]
+    w_global = float(ref.weight_sum(y, cw, hc["c"], hc["ignore_index"]))
+    out = {}
+    for world in (1, 2):
+        fn = str(tmp_path / ("step%d.npz" % world))
+        r = _run_ranks(world, worker, [fn, "sgd,adam"], timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        out[world] = dict(np.load(fn))
+        assert int(out[world].pop("world")) == world
+    bad = []
+    for opt in ("sgd", "adam"):
+        truth = ref.head_step(feats, y, cw, heads, opt)
+        for world in (1, 2):
+            got = {k[len(opt) + 1:]: v for k, v in out[world].items() if k.startswith(opt + "/")}
+            # every rank was handed W_global / world, and the mean of the ranks' loss values is the global loss
+            assert abs(float(got.pop("wsum")) * world - w_global) <= 1e-6 * w_global
+            got_ce = got.pop("ce")
+            for k in range(2):
+                err = abs(float(got_ce[k]) - ce[k]) / abs(ce[k])
+                print("%s world %d: CE of head %d, mean over ranks %.9e vs fp64 %.9e (rel %.2e)" % (opt, world, k + 1, float(got_ce[k]), ce[k], err))
+                assert err <= 2e-6, (opt, world, k, err)
+            assert got.keys() == truth.keys()
+            for k, t in truth.items():
+                t = t.numpy()
+                assert got[k].shape == t.shape and np.isfinite(got[k]).all(), k
+                err = float(np.abs(got[k] - t).max() / np.abs(t).max())
+                print("%s world %d %-12s %.2e of the largest entry from fp64 (bar 2e-5)" % (opt, world, k, err))
+                if not err <= 2e-5:
+                    bad.append((opt, world, k, err))
+    assert not bad, bad
+
+
 def test_bench_with_two_ranks_on_one_gpu():
     """``bench.py --gpus 2`` under a launcher, both ranks on cuda:0 over gloo: the multi-rank branch of the benchmark (per-rank
     batches, barrier + MAX-over-ranks timing, rank 0's single JSON line with the whole-job rate) on the real step."""
