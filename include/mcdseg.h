@@ -419,6 +419,47 @@ int mcdseg_up8_uncertain_loss_bwd(const float* s, const float* w_up, const float
  * out[n,y,x] = sum_{c < C_used} relu(up8(s, w_std))[n,c,y,x], fp32 [N,8Hi,8Wi], without the C-channel full-resolution tensor. */
 int mcdseg_up8_std_sum(const float* s, const float* w_std, float* out, int32_t N, int32_t C, int32_t C_used, int32_t Hi, int32_t Wi,
                        void* stream);
+/* The domain classifier of the DANN baseline (DRNSegDomainClassifier, models/dilated_fcn.py:494-551; dann_trainer.py:258-322), fused.
+ * csrc/dann.hip.  Everything fp32; no floating-point atomics, every sum in a fixed order: results are bit-identical from run to run.
+ *
+ * mcdseg_dann_down_fwd: one whole DownConv (models/dilated_fcn.py:506-531): y = maxpool2x2(relu(conv3x3(relu(conv3x3(x, w1) + b1), w2)
+ * + b2)), both convolutions with padding 1, x [N,Cin,H,W], w1 [Cmid,Cin,3,3], w2 [Cmid,Cmid,3,3], y [N,Cmid,H/2,W/2] (floor: the last
+ * row / column of an odd map takes no part in the pooling, as in torch).  The two full-resolution intermediates exist in LDS only.
+ * Nothing couples the samples, so N may be the batch of both domains.  Cmid = Cout is 1 or 10; Cin <= 50 at Cmid = 10 and <= 69 at
+ * Cmid = 1 (the backward's tile -- 24 x 24 pixels of every input channel plus three Cmid-channel regions -- must fit the 160 KB of
+ * LDS; both entry points refuse a larger shape and launch nothing).
+ * mcdseg_dann_down_bwd: dx (may be NULL: not wanted), dw1, db1, dw2, db2 for the upstream gradient dy [N,Cmid,H/2,W/2], recomputed
+ * from x and the weights.  A pooling window passes its gradient to its FIRST maximum in row-major order (torch's max_pool2d) and
+ * nothing where that maximum is a ReLU zero.  Parameter gradients: one partial per workgroup in `workspace`
+ * (mcdseg_dann_down_workspace_bytes), then an ordered second stage (a second launch) that sums each of the `groups` equal groups of
+ * samples (domains) by itself and then the groups in order: the gradients of a batch of both domains are, bit for bit, the sum of the
+ * gradients of one call per domain, which is what autograd accumulates.  The tail's parameter gradients are formed the same way.
+ *
+ * mcdseg_dann_tail_fwd: the rest of the classifier (models/dilated_fcn.py:547-551) and nn.CrossEntropyLoss (dann_trainer.py:244,
+ * 292-293, 318-319) for G groups (domains) of n rows each in one launch: h [G n, F] (the flattened second DownConv output),
+ * z = h w1^T + b1 (w1 [10,F]), BatchNorm1d(10), ReLU, logits [G n, 2] = a w2^T + b2 (w2 [2,10]), loss[g] = the mean over the rows of
+ * group g of the cross-entropy against labels[g] (int32 on the device, 0 or 1; any other value counts as 1).  training != 0: the
+ * statistics are PER GROUP -- biased variance normalises, running_mean / running_var take (1 - momentum) old + momentum new with the
+ * unbiased variance, group after group, as one module call per domain would; n >= 2 (torch refuses one row).  training == 0: the
+ * running statistics normalise and are left alone (--fix_bn).  save (mcdseg_dann_tail_save_bytes) keeps z and the statistics used.
+ * mcdseg_dann_tail_bwd: for one upstream scalar per group (upstream [G] on the device: -1 in the trainer's first update, +1 in its
+ * second) dh [G n, F] (may be NULL) and dw1, db1, dgamma, dbeta, dw2, db2; workspace: mcdseg_dann_tail_workspace_bytes.
+ * One workgroup each (the batch couples the rows; the problem is a few kilobytes); G <= 64. */
+size_t mcdseg_dann_down_workspace_bytes(int32_t N, int32_t Cin, int32_t Cmid, int32_t H, int32_t W);
+int mcdseg_dann_down_fwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, float* y, int32_t N,
+                         int32_t Cin, int32_t Cmid, int32_t H, int32_t W, void* stream);
+int mcdseg_dann_down_bwd(const float* x, const float* w1, const float* b1, const float* w2, const float* b2, const float* dy, float* dx,
+                         float* dw1, float* db1, float* dw2, float* db2, int32_t N, int32_t Cin, int32_t Cmid, int32_t H, int32_t W,
+                         int32_t groups, void* workspace, size_t workspace_bytes, void* stream);
+size_t mcdseg_dann_tail_save_bytes(int32_t G, int32_t n);
+size_t mcdseg_dann_tail_workspace_bytes(int32_t G, int32_t n);
+int mcdseg_dann_tail_fwd(const float* h, const int32_t* labels, const float* w1, const float* b1, const float* gamma, const float* beta,
+                         float* running_mean, float* running_var, const float* w2, const float* b2, float momentum, float eps,
+                         int32_t training, float* loss, float* logits, float* save, int32_t G, int32_t n, int32_t F, void* stream);
+int mcdseg_dann_tail_bwd(const float* h, const int32_t* labels, const float* w1, const float* gamma, const float* beta, const float* w2,
+                         const float* logits, const float* save, const float* upstream, float* dh, float* dw1, float* db1, float* dgamma,
+                         float* dbeta, float* dw2, float* db2, int32_t training, int32_t G, int32_t n, int32_t F, void* workspace,
+                         size_t workspace_bytes, void* stream);
 /* Depth image of the multitask tester (adapt_multitask_tester.py:148-155 with transform.py:285-294, unnormalize): d [N,Cd,Hi,Wi] fp32
  * (Cd = 1 or 3, the depth head) -> img [N,8Hi,8Wi,3] uint8 HWC.  v = bilinear x8 of d (mcdseg_bilinear8_fwd's fp32 values) in channel
  * Cd == 1 ? 0 : k; t = ((double)v * STD[k] + MEAN[k]) * 255 with every operation rounded in double (numpy's promotion against the

@@ -31,6 +31,8 @@ def main(argv=None, mfnet=False):
     method = getattr(train_args, "method", "MCD")
     if mfnet:  # the trainer stores the full "MFNet-<fusion>" name in method_detail (adapt_mfnet_trainer.py:29)
         method = train_args.method_detail if "MFNet" in train_args.method_detail else method + "-" + train_args.method_detail
+    if method == "DANN":  # dann_trainer.py's G and F are MCD's G and F1; its checkpoint holds no F2 (and a D, which inference does not use)
+        method = "MCD"
     *encoders, F1, F2 = get_models(net_name=train_args.net, res=train_args.res, input_ch=train_args.input_ch, n_class=train_args.n_class,
                                    method=method, is_data_parallel=getattr(train_args, "is_data_parallel", False))
     for G, key in zip(encoders, ("g_3ch_state_dict", "g_1ch_state_dict") if mfnet else ("g_state_dict",)):

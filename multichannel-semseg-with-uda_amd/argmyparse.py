@@ -112,6 +112,13 @@ def get_da_mcd_training_parser():
     return parser
 
 
+def get_da_dann_training_parser():
+    """argmyparse.py:140-143 of the reference"""
+    parser = get_da_base_training_parser()
+    parser.add_argument("--method", type=str, default="DANN", help="Method Name")
+    return parser
+
+
 def get_da_mcd_testing_parser():
     """flags of the reference's testers (argmyparse.py:146-160)"""
     parser = argparse.ArgumentParser(description="Adapt tester for validation data")

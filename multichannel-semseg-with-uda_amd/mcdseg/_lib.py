@@ -56,6 +56,13 @@ _SIGNATURES = {
     "mcdseg_up8_uncertain_loss_bwd": (c_int, [c_void_p] * 5 + [c_i64, c_void_p, c_void_p, c_float, c_void_p, c_float] + [c_void_p] * 4 +
                                       [c_i32] * 5 + [c_void_p]),
     "mcdseg_up8_std_sum": (c_int, [c_void_p] * 3 + [c_i32] * 5 + [c_void_p]),
+    "mcdseg_dann_down_workspace_bytes": (c_size_t, [c_i32] * 5),
+    "mcdseg_dann_down_fwd": (c_int, [c_void_p] * 6 + [c_i32] * 5 + [c_void_p]),
+    "mcdseg_dann_down_bwd": (c_int, [c_void_p] * 11 + [c_i32] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_dann_tail_save_bytes": (c_size_t, [c_i32] * 2),
+    "mcdseg_dann_tail_workspace_bytes": (c_size_t, [c_i32] * 2),
+    "mcdseg_dann_tail_fwd": (c_int, [c_void_p] * 10 + [c_float, c_float, c_i32] + [c_void_p] * 3 + [c_i32] * 3 + [c_void_p]),
+    "mcdseg_dann_tail_bwd": (c_int, [c_void_p] * 16 + [c_i32] * 4 + [c_void_p, c_size_t, c_void_p]),
     "mcdseg_depth_image_u8": (c_int, [c_void_p, c_void_p] + [c_i32] * 4 + [c_void_p]),
     "mcdseg_absmax": (c_int, [c_void_p, c_i64, c_void_p, c_void_p]),
     "mcdseg_conv_split_packed_bytes": (c_int, [_P(ConvDesc), c_i32, _P(c_i64), _P(c_i64)]),
@@ -183,7 +190,7 @@ def sources():
 # backward under two ranks per device.  The compiler forms these instructions on its own from scalar fp32 source code, so the
 # files below are compiled with the packed-fp32 feature off, and ``packed_f32_opsel_sites`` (tests/test_cabi_and_host.py)
 # disassembles the built library to prove that no such instruction is left in ANY kernel.
-NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip", "seg2bd.hip", "augment.hip", "uncertain.hip"}
+NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip", "seg2bd.hip", "augment.hip", "uncertain.hip", "dann.hip"}
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden"]
 NO_PK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # (the host pass ignores it with a warning)
 OBJ_DIR = os.path.join(CSRC, "build")

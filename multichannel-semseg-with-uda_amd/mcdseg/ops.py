@@ -2238,6 +2238,100 @@ def up8_std_sum(s, w_std, n_used=None):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ the DANN domain classifier (csrc/dann.hip)
+class _DannDown(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, groups):
+        x, w1, b1, w2, b2 = _req(x, "DownConv input"), _req(w1, "conv1.weight"), _req(b1, "conv1.bias"), _req(w2, "conv2.weight"), _req(b2, "conv2.bias")
+        n, cin, h, w = x.shape
+        cm = w1.shape[0]
+        if tuple(w1.shape) != (cm, cin, 3, 3) or tuple(w2.shape) != (cm, cm, 3, 3) or b1.numel() != cm or b2.numel() != cm:
+            raise ValueError("mcdseg: DownConv weights %s / %s do not fit an input of %d channels" % (tuple(w1.shape), tuple(w2.shape), cin))
+        y = torch.empty((n, cm, h // 2, w // 2), dtype=torch.float32, device=x.device)
+        with _timed("dann_down_fwd_kernel<%d>" % cm, (2 * 9 * n * h * w * cm * (cin + cm), 4 * (x.numel() + y.numel()))):
+            check(lib().mcdseg_dann_down_fwd(_p(x), _p(w1), _p(b1), _p(w2), _p(b2), _p(y), n, cin, cm, h, w, _stream()), "dann_down_fwd")
+        ctx.save_for_backward(x, w1, b1, w2, b2)
+        ctx.groups = int(groups)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w1, b1, w2, b2 = ctx.saved_tensors
+        n, cin, h, w = x.shape
+        cm = w1.shape[0]
+        dy = _req(dy, "grad_output")
+        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        dw1, db1, dw2, db2 = torch.empty_like(w1), torch.empty_like(b1), torch.empty_like(w2), torch.empty_like(b2)
+        ws = _ws(lib().mcdseg_dann_down_workspace_bytes(n, cin, cm, h, w), x.device)
+        with _timed("dann_down_bwd_kernel<%d>" % cm, (2 * 9 * n * h * w * cm * (4 * cin + 3 * cm), 4 * (2 * x.numel() + dy.numel()))):
+            check(lib().mcdseg_dann_down_bwd(_p(x), _p(w1), _p(b1), _p(w2), _p(b2), _p(dy), _p(dx), _p(dw1), _p(db1), _p(dw2), _p(db2), n, cin, cm,
+                                             h, w, ctx.groups, _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()), "dann_down_bwd")
+        _on_launch_stream(ws)
+        return dx, dw1, db1, dw2, db2, None
+
+
+def dann_down(x, w1, b1, w2, b2, groups=1):
+    """One ``DownConv`` of the domain classifier (models/dilated_fcn.py:506-531) in one launch each way:
+    ``max_pool2d(relu(conv3x3(relu(conv3x3(x, w1) + b1), w2) + b2), 2, 2)``; include/mcdseg.h has the shapes it takes.  ``groups``: the
+    batch holds that many equal groups of samples (domains) whose parameter gradients are summed group by group, so that they equal
+    the sum of one call per group bit for bit."""
+    return _DannDown.apply(x, w1, b1, w2, b2, groups)
+
+
+class _DannTail(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, w1, b1, gamma, beta, w2, b2, labels, running_mean, running_var, momentum, eps, training):
+        L = lib()
+        h, w1, b1, gamma, beta, w2, b2 = (_req(t, name) for t, name in ((h, "tail input"), (w1, "fc1.weight"), (b1, "fc1.bias"), (gamma, "bn1.weight"),
+                                                                         (beta, "bn1.bias"), (w2, "fc2.weight"), (b2, "fc2.bias")))
+        labels = _req(labels, "domain labels", torch.int32)
+        rm, rv = _req(running_mean, "bn1.running_mean"), _req(running_var, "bn1.running_var")
+        if rm is not running_mean or rv is not running_var:
+            raise ValueError("mcdseg: the running statistics are updated in place and must be contiguous")
+        groups = labels.numel()
+        rows, f = h.shape
+        if groups < 1 or rows % groups or tuple(w1.shape) != (10, f) or tuple(w2.shape) != (2, 10):
+            raise ValueError("mcdseg: tail input %s, %d groups, fc1 %s, fc2 %s do not fit" % (tuple(h.shape), groups, tuple(w1.shape), tuple(w2.shape)))
+        n = rows // groups
+        loss = torch.empty(groups, dtype=torch.float32, device=h.device)
+        logits = torch.empty((rows, 2), dtype=torch.float32, device=h.device)
+        save = _ws64(L.mcdseg_dann_tail_save_bytes(groups, n), h.device)
+        with _timed("dann_tail_fwd_kernel", (2 * rows * 10 * f, 4 * (h.numel() + w1.numel()))):
+            check(L.mcdseg_dann_tail_fwd(_p(h), _p(labels), _p(w1), _p(b1), _p(gamma), _p(beta), _p(rm), _p(rv), _p(w2), _p(b2), float(momentum),
+                                         float(eps), int(bool(training)), _p(loss), _p(logits), _p(save), groups, n, f, _stream()), "dann_tail_fwd")
+        ctx.save_for_backward(h, w1, gamma, beta, w2, labels, logits, save)
+        ctx.training = int(bool(training))
+        ctx.mark_non_differentiable(logits)
+        return loss, logits
+
+    @staticmethod
+    def backward(ctx, gl, _glogits):
+        h, w1, gamma, beta, w2, labels, logits, save = ctx.saved_tensors
+        L = lib()
+        groups = labels.numel()
+        rows, f = h.shape
+        n = rows // groups
+        up = _req(gl.reshape(groups), "grad_output")
+        dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None
+        dw1, db1, dgamma, dbeta, dw2, db2 = (torch.empty(s, dtype=torch.float32, device=h.device) for s in ((10, f), (10,), (10,), (10,), (2, 10), (2,)))
+        ws = _ws(L.mcdseg_dann_tail_workspace_bytes(groups, n), h.device)
+        with _timed("dann_tail_bwd_kernel", (4 * rows * 10 * f, 4 * (3 * h.numel() + 2 * w1.numel()))):
+            check(L.mcdseg_dann_tail_bwd(_p(h), _p(labels), _p(w1), _p(gamma), _p(beta), _p(w2), _p(logits), _p(save), _p(up), _p(dh), _p(dw1), _p(db1),
+                                         _p(dgamma), _p(dbeta), _p(dw2), _p(db2), ctx.training, groups, n, f, _p(ws), ctypes.c_size_t(ws.numel() * 4),
+                                         _stream()), "dann_tail_bwd")
+        _on_launch_stream(ws)
+        return (dh, dw1, db1, dgamma, dbeta, dw2, db2) + (None,) * 6
+
+
+def dann_tail(h, fc1_weight, fc1_bias, bn_weight, bn_bias, fc2_weight, fc2_bias, labels, running_mean, running_var, momentum=0.1, eps=1e-5,
+              training=True):
+    """The domain classifier behind its two ``DownConv``s (models/dilated_fcn.py:547-551) and ``nn.CrossEntropyLoss`` against one domain label
+    per group, all groups in one launch each way: ``h`` [G n, F] holds G groups of n rows, ``labels`` int32 [G] on the device.  Returns
+    (loss [G], the mean cross-entropy of each group; logits [G n, 2], not differentiable).  BatchNorm1d's statistics are per group in
+    training mode, and the running statistics are updated in place, group after group; include/mcdseg.h has the rest."""
+    return _DannTail.apply(h, fc1_weight, fc1_bias, bn_weight, bn_bias, fc2_weight, fc2_bias, labels, running_mean, running_var, momentum, eps, training)
+
+
 def predict_labels(z1, z2=None, n_used=None):
     """Inference tail of adapt_tester.py:101-124: (uint8 label map [N,H,W] = argmax over the first ``n_used`` classes
     of z1 or (z1+z2)/2, mean entropy scalar as util.calc_entropy defines it)."""

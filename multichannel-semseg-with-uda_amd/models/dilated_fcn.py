@@ -4,6 +4,7 @@
   UncertainDRNSeg                     :113-214  DRNSeg + ``up_std`` and the Monte-Carlo dropout loss, all draws in one kernel
   DRNSegBase                = G       :217-250  trunk + 1x1 ``seg`` (ver1) / trunk only (ver2)
   DRNSegPixelClassifier     = F1/F2   :340-366  learned x8 depthwise transposed-conv up-sampler
+  DownConv / DRNSegDomainClassifier = D  :494-551  the DANN baseline's domain classifier, three fused launches each way
   FusionDRNSegPixelClassifier         :431-470  fuse features, one up-sampler
   ScoreFusionDRNSegPixelClassifier    :473-491  one up-sampler per modality, fuse scores
   MultiTaskEncoder / MCDMultiTaskDecoder            :554-566, 661-739   segmentation + HHA regression (cfg4)
@@ -253,6 +254,117 @@ class DRNSegPixelClassifier(nn.Module):
         if self.ver == "ver2":
             x = self.seg(x)
         return self.up(x)
+
+
+def score_map_hw(trunk, h, w):
+    """(rows, columns) of the score map the DRN trunk makes of an h x w image, read off the trunk itself: every stage that strides
+    does so in its first strided convolution (the shortcut projection beside it strides alike), the others keep the size"""
+    for stage in trunk.children():
+        conv = next((m for m in stage.modules() if isinstance(m, nn.Conv2d) and m.stride[0] > 1), None)
+        if conv is not None:
+            k, s, p, d = conv.kernel_size[0], conv.stride[0], conv.padding[0], conv.dilation[0]
+            h, w = ((v + 2 * p - d * (k - 1) - 1) // s + 1 for v in (h, w))
+    return h, w
+
+
+def domain_fc_in(model_g, img_shape):
+    """``fc1``'s width for a domain classifier behind ``model_g`` at ``--train_img_shape``: the score map, pooled 2x2 twice with floor
+    division, one channel.  1089 at 1080 x 1080, the only size the reference's hard-coded Linear(1089, 10) fits."""
+    a, b = score_map_hw(model_g.base, int(img_shape[0]), int(img_shape[1]))
+    return (a // 2 // 2) * (b // 2 // 2)
+
+
+class _LogitsOnly(torch.autograd.Function):
+    """the logits ``DRNSegDomainClassifier.forward`` returns: values only -- a backward pass through them says where the gradient is"""
+
+    @staticmethod
+    def forward(ctx, logits, anchor):
+        return logits.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        raise RuntimeError("DRNSegDomainClassifier.forward(x) returns logits without a gradient: the fused kernels differentiate the "
+                           "cross-entropy they compute.  Use model_d.domain_loss(x, label) for criterion_d(model_d(x), label), or "
+                           "model_d.forward_pair(src_fet, tgt_fet) for both domains at once.")
+
+
+class DownConv(nn.Module):
+    """conv3x3+bias, ReLU, conv3x3+bias, ReLU, MaxPool2d(2, 2) (models/dilated_fcn.py:506-531) as ONE kernel each way
+    (csrc/dann.hip); ``conv1`` / ``conv2`` hold the parameters in torch's layout and default initialisation."""
+
+    def __init__(self, in_channels, out_channels, pooling=True):
+        super().__init__()
+        if not pooling:
+            raise NotImplementedError("DownConv without pooling is not part of the domain classifier")
+        self.in_channels, self.out_channels, self.pooling = in_channels, out_channels, pooling
+        self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True)
+        self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=True)
+
+    def forward(self, x, groups=1):
+        return ops.dann_down(x, self.conv1.weight, self.conv1.bias, self.conv2.weight, self.conv2.bias, groups)
+
+
+class DRNSegDomainClassifier(nn.Module):
+    """D of the DANN baseline (models/dilated_fcn.py:534-551): DownConv(n_class, 10), DownConv(10, 1), flatten, Linear(fc_in, 10),
+    BatchNorm1d(10), ReLU, Linear(10, 2) on G's 1/8-resolution score map -- two DownConv launches and one launch for everything behind
+    them, the two-class cross-entropy included (``ops.dann_down``, ``ops.dann_tail``).  State-dict keys and shapes are the reference's.
+
+    ``fc_in`` is a departure: the reference hard-codes 1089 = 33 x 33, which fits 1080 x 1080 images only ("TODO This is for 4ch");
+    the trainer passes ``domain_fc_in`` of its image size, which is 1089 there.
+
+    ``forward_pair(src_fet, tgt_fet)`` is what the trainer calls: both domains through the three launches at once, BatchNorm1d
+    statistics per domain and the running statistics updated source first, as the reference's two calls would -- it returns the two
+    mean cross-entropies (source against label 1, target against 0) and the logits.  ``domain_loss(x, label)`` is one domain alone.
+    ``forward(x)`` keeps the reference's signature and returns the logits of one domain through the same kernels; the kernels
+    differentiate the cross-entropy they compute, so these logits carry no gradient: a backward pass through them raises an error
+    that names ``domain_loss`` and ``forward_pair``."""
+
+    def __init__(self, n_class, fc_in=1089):
+        super().__init__()
+        self.conv1 = DownConv(n_class, 10)
+        self.conv2 = DownConv(10, 1)
+        self.fc1 = nn.Linear(fc_in, 10)
+        self.bn1 = nn.BatchNorm1d(10)
+        self.fc2 = nn.Linear(10, 2)
+        self._labels = {}
+
+    def _domain_labels(self, labels, device):
+        key = (tuple(int(v) for v in labels), str(device))
+        if key not in self._labels:
+            self._labels[key] = torch.tensor(key[0], dtype=torch.int32, device=device)
+        return self._labels[key]
+
+    def _run(self, x, labels):
+        h = self.conv2(self.conv1(x, len(labels)), len(labels))
+        h = h.view(h.size(0), -1)
+        if h.size(1) != self.fc1.in_features:
+            raise ValueError("DRNSegDomainClassifier: a %dx%d score map pools to %d features, fc1 takes %d (build the classifier with "
+                             "fc_in=%d)" % (x.size(2), x.size(3), h.size(1), self.fc1.in_features, h.size(1)))
+        bn = self.bn1
+        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+            raise NotImplementedError("the fused tail takes BatchNorm1d as the reference builds it (affine, running statistics, a momentum)")
+        loss, logits = ops.dann_tail(h, self.fc1.weight, self.fc1.bias, bn.weight, bn.bias, self.fc2.weight, self.fc2.bias,
+                                     self._domain_labels(labels, x.device), bn.running_mean, bn.running_var, bn.momentum, bn.eps, bn.training)
+        if bn.training:
+            bn.num_batches_tracked += len(labels)  # (one module call per domain in the reference)
+        return loss, logits
+
+    def forward(self, x):
+        logits = self._run(x, (0,))[1]
+        if torch.is_grad_enabled() and self.fc2.weight.requires_grad:  # (so that a backward pass through them raises OUR message)
+            return _LogitsOnly.apply(logits, self.fc2.weight)
+        return logits
+
+    def domain_loss(self, x, label):
+        """(mean cross-entropy of ``x``'s rows against the one domain ``label``, logits)"""
+        loss, logits = self._run(x, (label,))
+        return loss[0], logits
+
+    def forward_pair(self, src_fet, tgt_fet, labels=(1, 0)):
+        """(loss [2]: source against labels[0], target against labels[1]; logits [2n, 2], source rows first)"""
+        if src_fet.shape != tgt_fet.shape:
+            raise ValueError("forward_pair: the two domains' score maps differ in shape: %s, %s" % (tuple(src_fet.shape), tuple(tgt_fet.shape)))
+        return self._run(torch.cat([src_fet, tgt_fet]), labels)
 
 
 class FusionDRNSegPixelClassifier(nn.Module):

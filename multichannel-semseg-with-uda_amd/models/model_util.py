@@ -81,6 +81,17 @@ def get_models(net_name, input_ch, n_class, res="50", method="MCD", is_data_para
     return _wrap(model_list, is_data_parallel)
 
 
+def get_dann_models(net_name, input_ch, n_class, img_shape, res="50"):
+    """G, F and the domain classifier D of the DANN baseline (dann_trainer.py:132-141 of the reference); D's ``fc1`` is as wide as G's
+    score map at ``img_shape`` makes it (models/dilated_fcn.domain_fc_in; 1089, the reference's constant, at 1080 x 1080)."""
+    if "drn" not in net_name:
+        raise NotImplementedError("Only FCN, SegNet, PSPNet are supported!")  # (the reference's text, dann_trainer.py:141)
+    from models.dilated_fcn import DRNSegBase, DRNSegDomainClassifier, DRNSegPixelClassifier, domain_fc_in
+    assert net_name in DRN_NAMES
+    model_g = DRNSegBase(model_name=net_name, n_class=n_class, input_ch=input_ch, pretrained=_pretrained_default())
+    return model_g, DRNSegPixelClassifier(n_class=n_class), DRNSegDomainClassifier(n_class=n_class, fc_in=domain_fc_in(model_g, img_shape))
+
+
 def get_multitask_models(net_name, input_ch, n_class, semseg_criterion=None, discrepancy_criterion=None,
                          is_data_parallel=False, is_src_only=False):
     """RGB encoder + MCD multitask decoder (models/model_util.py:81-99); the source-only decoder variant is not on

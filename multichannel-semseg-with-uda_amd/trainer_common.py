@@ -161,6 +161,7 @@ class Trainer:
     on_resume: typing.Callable = None     # (pickled args, command-line args): what the command line still decides on resume
     announces_resume: bool = False        # the two "=> load..." lines of adapt_trainer.py
     src_input_ch: int = None              # channels of the source batch where they are not --input_ch (None: --input_ch, as for the target)
+    lr_adjusted: tuple = None             # keys of the optimizers whose learning rate --adjust_lr adjusts (None: all of them)
 
 
 Layout = collections.namedtuple("Layout", "pth_dir tflog_dir json_fn model_name")
@@ -223,6 +224,12 @@ def criteria(args, device=None, cross_entropy=CrossEntropyLoss2d):
 
 def mcd_report(epoch, sums, modules):
     print("Epoch [%d] DLoss: %.4f CLoss: %.4f" % (epoch, sums["d_loss"], sums["c_loss"]))
+
+
+def lr_adjusted_optimizers(trainer, optimizers):
+    """the optimizers ``--adjust_lr`` touches, in the order they were declared"""
+    keys = tuple(optimizers) if trainer.lr_adjusted is None else trainer.lr_adjusted
+    return [optimizers[k] for k in keys]
 
 
 def _resume_or_build(trainer, run, cli):
@@ -299,7 +306,7 @@ def train(trainer, args):
             run.log_value(name, sums[name], epoch)
         run.log_value("lr", args.lr, epoch)
         if args.adjust_lr:  # the reference passes weight_decay as the decay rate (adapt_trainer.py:228-230)
-            for optimizer in optimizers.values():
+            for optimizer in lr_adjusted_optimizers(trainer, optimizers):
                 args.lr = adjust_learning_rate(optimizer, args.lr, args.weight_decay, epoch, args.epochs)
         args.start_epoch = epoch + 1
         run.save(checkpoint_dict(args, epoch + 1, modules, optimizers), checkpoint_fn(layout, epoch + 1))
