@@ -245,6 +245,16 @@ int mcdseg_split_cb(const float* x, void* x_cb, const float* x_bound, int32_t ma
 int mcdseg_split_cb_padded(const float* x, void* x_cb, const float* x_bound, int32_t math, int32_t N, int32_t C, int32_t HW,
                            void* stream);
 int mcdseg_unsplit_cb(const void* x_cb, const float* x_bound, int32_t math, int32_t N, int32_t C, int32_t HW, float* x, void* stream);
+/* The stage join of the FuseNet-style generator: x = torch.add(x, x_dk) behind every stage of the RGB pass
+ * (FuseDRNSegBase.forward, models/dilated_fcn.py:308-328).  y = a + b (fp32 NCHW, the fp32 add and nothing else) and, y_cb != NULL,
+ * the companion of y for the next stage's convolutions in the same pass: [piece][N][C/8][HW][8 x 16 bit], bitwise what
+ * mcdseg_split_cb(y, y_bound) writes.  Nothing is reduced: |a + b| <= a_bound[0] + b_bound[0], and y_bound[0] is that one fp32 sum
+ * (the scale is at most one power of two coarser than a measured bound would give).  MCDSEG_MATH_F16X3 / _F16X1 need the three bound
+ * pointers; MCDSEG_MATH_BF16X6 takes them as NULL (all three or none: given, y_bound is written all the same).  y_cb == NULL: any C,
+ * only y (and y_bound, when the bounds are given) is written, `math` is not read.  With a companion the refusals of mcdseg_split_cb
+ * apply (C % 8, N * C/8 > 65535); every refusal is answered before anything is launched. */
+int mcdseg_stage_join(const float* a, const float* a_bound, const float* b, const float* b_bound, float* y, void* y_cb, float* y_bound,
+                      int32_t math, int32_t N, int32_t C, int32_t HW, void* stream);
 int mcdseg_bn_apply_cb(const float* z, const float* mean, const float* rstd, const float* gamma, const float* beta,
                        const float* residual, const void* res_cb, const float* res_bound, float* y, void* y_cb,
                        const float* y_bound, int32_t math, int32_t N, int32_t C, int32_t HW, int32_t relu, void* stream);

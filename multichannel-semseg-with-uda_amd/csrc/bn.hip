@@ -545,14 +545,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
 // of inside the convolution's K loop (where every activation is re-split for each of the 9 taps and 4 M-tiles and the
 // conversion competes with MFMA issue slots) is worth ~1.3x on the convolution.  One thread = one pixel x 8 channels:
 // loads and fp32 stores are pixel-contiguous per channel, the 16-B split stores are contiguous across lanes.
-template <class P>
-__device__ __forceinline__ void split_store(const float (&v)[8], float inv_scale, typename P::elem* __restrict__ cb, size_t piece_stride,
-                                            size_t idx16) {
-  typename P::frag pieces[P::NP];
-  split_frag<P>(v, inv_scale, pieces);
-#pragma unroll
-  for (int pc = 0; pc < P::NP; ++pc) *reinterpret_cast<typename P::frag*>(cb + pc * piece_stride + idx16 * 8) = pieces[pc];
-}
+// (split_store<P>, the store of one such unit, is in split.h: csrc/join.hip writes companions too)
 
 // the inverse: 8 channels of one pixel back from the companion, value = scale * (sum of the pieces) -- exact for the bf16
 // split, the 22 leading bits for the fp16 one
@@ -1096,14 +1089,6 @@ extern "C" int mcdseg_bn_apply(const float* z, const float* mean, const float* r
     hipLaunchKernelGGL(bn_apply_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, z, mean, rstd, gamma, beta, residual, y, C,
                        HW, relu);
   MCD_LAUNCH_CHECK("bn_apply");
-  return 0;
-}
-
-static int cb_check(const char* who, int32_t math, const float* bound, int32_t N, int32_t C, int32_t HW) {
-  MCD_REQUIRE(math == MCDSEG_MATH_BF16X6 || math == MCDSEG_MATH_F16X3, "%s: unknown math %d", who, math);
-  MCD_REQUIRE(math != MCDSEG_MATH_F16X3 || bound != nullptr, "%s: the f16x3 split needs the bound scalar of the tensor", who);
-  MCD_REQUIRE(N > 0 && C > 0 && HW > 0 && (C % 8) == 0, "%s: C must be a positive multiple of 8", who);
-  MCD_REQUIRE((int64_t)N * (C / 8) <= 65535, "%s: N*C/8 exceeds the grid limit", who);
   return 0;
 }
 

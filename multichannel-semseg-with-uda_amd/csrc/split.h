@@ -122,10 +122,30 @@ __device__ __forceinline__ float operand_scale(const float* bound) {
   return 1.f;
 }
 
+// one unit of a companion in the channel-blocked layout cb[piece NP][N][C/8][HW][8 x 16 bit] (bn.hip, "cb" variants): the split of 8
+// channels of one pixel, one 16-byte store per piece; idx16 = (n * C/8 + g) * HW + pixel
+template <class P>
+__device__ __forceinline__ void split_store(const float (&v)[8], float inv_scale, typename P::elem* __restrict__ cb, size_t piece_stride,
+                                            size_t idx16) {
+  typename P::frag pieces[P::NP];
+  split_frag<P>(v, inv_scale, pieces);
+#pragma unroll
+  for (int pc = 0; pc < P::NP; ++pc) *reinterpret_cast<typename P::frag*>(cb + pc * piece_stride + idx16 * 8) = pieces[pc];
+}
+
 static inline int mcd_math_pieces(int math) { return (math == 3 || math == 1) ? 2 : 3; }  // MCDSEG_MATH_F16X3 / _F16X1 : MCDSEG_MATH_BF16X6
 // the arithmetic whose STORAGE (companions, weight images, bounds) a math shares: F16X1 multiplies F16X3's operands
 static inline int mcd_storage_math(int math) { return math == 1 ? 3 : math; }
 static inline bool mcd_math_known(int math) { return math == 1 || math == 3 || math == 6; }
+
+// what every entry point that reads or writes a companion refuses before it launches (`math`: the storage math, mcd_storage_math)
+static inline int cb_check(const char* who, int32_t math, const float* bound, int32_t N, int32_t C, int32_t HW) {
+  MCD_REQUIRE(math == MCDSEG_MATH_BF16X6 || math == MCDSEG_MATH_F16X3, "%s: unknown math %d", who, math);
+  MCD_REQUIRE(math != MCDSEG_MATH_F16X3 || bound != nullptr, "%s: the f16x3 split needs the bound scalar of the tensor", who);
+  MCD_REQUIRE(N > 0 && C > 0 && HW > 0 && (C % 8) == 0, "%s: C must be a positive multiple of 8", who);
+  MCD_REQUIRE((int64_t)N * (C / 8) <= 65535, "%s: N*C/8 exceeds the grid limit", who);
+  return 0;
+}
 
 // ---- transposing LDS reads (ds_read_b64_tr_b16): the MFMA fragments of the weight-gradient kernels whose operands sit in LDS as in
 // memory, 16-byte units of 8 channels x 1 pixel (conv_wgrad_split.hip, conv_wgrad_split_pp.hip) ----------------------------------

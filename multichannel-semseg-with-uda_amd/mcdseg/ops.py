@@ -5,6 +5,7 @@ pass over activations, gradients and parameters below is a hand-written HIP kern
 mirror the ATen call sites of the reference's hot path:
 
   conv_bn_act      nn.Conv2d + nn.BatchNorm2d + ReLU (+ residual)   models/drn.py:43-59, 80-100, 195-205
+  stage_join       torch.add between two stage outputs (+ the next stage's operand)   models/dilated_fcn.py:308-328
   conv2d_bias      nn.Conv2d with bias (the 1x1 ``seg`` head)       models/dilated_fcn.py:226-232
   up8 / up8_dual   depthwise ConvTranspose2d k16 s8 p4              models/dilated_fcn.py:357-366, 479-491
   cross_entropy2d  log_softmax + weighted NLL                       loss.py:7-13
@@ -1584,6 +1585,69 @@ def _cb_of(x):
     if cb is not None and cb.numel() != PIECES.get(CONV_MATH, 0) * x.numel() and not (CONV_MATH == "f16x1" and cb.numel() == x.numel()):
         cb = None  # (f16x1 reads the leading piece only: a one-piece companion of the 2-byte chain serves every consumer)
     return cb, (bound if _scaled() else None)
+
+
+# ------------------------------------------------------------------------------------------------ stage join (middle fusion)
+def fused_join():
+    """MCDSEG_FUSED_JOIN=0 (host-side, read at every call): ``stage_join`` composes its result from ``a + b`` and ``split_companion``
+    with the bound ``bound_a + bound_b`` instead of the one-pass kernel -- bitwise the same; the parity test's other side and the
+    timing baseline"""
+    return os.environ.get("MCDSEG_FUSED_JOIN", "1") != "0"
+
+
+class _StageJoin(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, a_bound, b_bound, want_cb, fused):
+        n, c, h, w = a.shape
+        hw = h * w
+        y_bound = None
+        if fused:
+            y = torch.empty_like(a)
+            y_cb = _cb_alloc(n, c, hw, a.device) if want_cb else None
+            if a_bound is not None:
+                y_bound = torch.empty(1, dtype=torch.float32, device=a.device)
+            cb_bytes = 2 * PIECES[CONV_MATH] if want_cb else 0
+            with _timed("stage_join", (0, n * c * hw * (12 + cb_bytes))):
+                check(lib().mcdseg_stage_join(_p(a), _p(a_bound), _p(b), _p(b_bound), _p(y), _p(y_cb), _p(y_bound), MATH_ID.get(CONV_MATH, 0),
+                                              n, c, hw, _stream()), "stage_join")
+        else:
+            y = a + b
+            if a_bound is not None:
+                y_bound = a_bound + b_bound
+            y_cb = split_companion(y, y_bound)[0] if want_cb else None
+        ctx.set_materialize_grads(False)
+        for t in (y_cb, y_bound):
+            if t is not None:
+                ctx.mark_non_differentiable(t)
+        return y, y_cb, y_bound
+
+    @staticmethod
+    def backward(ctx, dy, _dcb=None, _dbound=None):
+        return dy, dy, None, None, None, None  # d(a + b): the incoming gradient, to both
+
+
+def stage_join(a, b):
+    """y = a + b between two stage outputs of the FuseNet-style generator (models/dilated_fcn.py FuseDRNSegBase), with what the next
+    stage's convolutions read attached to ``y`` the way ``conv_bn_act`` attaches it: the pre-split companion -- exactly when
+    ``_cb_wanted(C)`` and the grid fits -- and the bound ``bound_a + bound_b`` (|a + b| cannot exceed it: nothing is measured unless a
+    producer supplied no bound).  The incoming gradient goes to both inputs.  Without grad mode and with inputs that carry neither a
+    companion nor a bound (the folded-BN inference kernels write none, and read none) only ``y`` is written."""
+    if is_virtual(a) or is_virtual(b):
+        raise RuntimeError("mcdseg: stage_join takes fp32 stage outputs, not activations kept as their companions")
+    if a.shape != b.shape or a.dim() != 4:
+        raise ValueError("mcdseg: stage_join takes two NCHW tensors of one shape, got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    a, b = _req(a, "stage_join input"), _req(b, "stage_join input")
+    n, c = a.shape[0], a.shape[1]
+    recs = (_cb_of(a), _cb_of(b))
+    plain = not torch.is_grad_enabled() and all(cb is None and bound is None for cb, bound in recs)
+    want_cb = bool(not plain and _cb_wanted(c) and _cb_grid_ok(n, c))
+    a_bound = b_bound = None
+    if _scaled() and not plain and (want_cb or _use_split(c)):
+        a_bound, b_bound = _bound_or_measure(a, recs[0][1]), _bound_or_measure(b, recs[1][1])
+    y, y_cb, y_bound = _StageJoin.apply(a, b, a_bound, b_bound, want_cb, fused_join())
+    if y_cb is not None or y_bound is not None:
+        y._mcd_cb = (y_cb, y_bound, y._version, y.data_ptr())
+    return y
 
 
 # ------------------------------------------------------------------------------------------------ conv (+bias)

@@ -3,6 +3,7 @@
   DRNSeg                              :68-110   trunk + seg + up (source-only training, cfg1)
   UncertainDRNSeg                     :113-214  DRNSeg + ``up_std`` and the Monte-Carlo dropout loss, all draws in one kernel
   DRNSegBase                = G       :217-250  trunk + 1x1 ``seg`` (ver1) / trunk only (ver2)
+  FuseDRNSegBase            = G       :253-337  middle fusion: one set of DRN-D stages on HHA, then on RGB, a join behind every stage
   DRNSegPixelClassifier     = F1/F2   :340-366  learned x8 depthwise transposed-conv up-sampler
   DownConv / DRNSegDomainClassifier = D  :494-551  the DANN baseline's domain classifier, three fused launches each way
   FusionDRNSegPixelClassifier         :431-470  fuse features, one up-sampler
@@ -239,6 +240,75 @@ class DRNSegBase(nn.Module):
     def optim_parameters(self, memo=None):
         yield from self.base.parameters()
         yield from self.seg.parameters()
+
+
+def _walk_stage(stage, x):
+    """one DRN stage with an ordinary fp32 output (the stage-tap walk of ``MultiTaskEncoderReturningMultipleFeaturemaps``)"""
+    if type(stage) is FusedSequential and not _has_hooks(stage):
+        return run_fused(list(stage.children()), x)
+    return stage(x)
+
+
+class FuseDRNSegBase(nn.Module):
+    """G of the middle fusion (``--net drn_d_XX_fusenet``; models/dilated_fcn.py:253-337): ONE set of DRN-D stages ``main_layer0`` ..
+    ``main_layer8`` runs twice per forward -- on the HHA channels first, keeping every stage output ``x_dk``, then on the RGB channels
+    with ``x = main_layerk(x) + x_dk`` behind every stage (``ops.stage_join``) -- and the 1x1 ``seg`` head scores the last sum.  The
+    weights are shared: each convolution's weight gradient is the sum of both uses, each train-mode BatchNorm takes its batch statistics
+    per call and updates its running statistics twice, HHA then RGB (``num_batches_tracked`` grows by 2 per forward).
+
+    ``sub_layer0`` .. ``sub_layer8`` -- a second trunk for ``input_ch - 3`` channels -- are built and never called, as in the reference:
+    the state-dict keys are the reference's and its checkpoints load.  Their parameters carry ``requires_grad = False``: in the reference
+    they never receive a gradient, so no optimizer touches them (weight decay included); here they enter no flat buffer either.
+
+    Departures: ``input_ch`` must be 6 (with 4 the reference feeds one channel to the 3-channel ``main_layer0`` and raises), only DRN-D
+    (the reference asserts it), no ``ver2`` (the reference has no such constructor), no ``optim_parameters`` (the reference's reads a
+    ``self.base`` that does not exist).  Every stage output is needed as fp32 -- it has two readers -- so compact activation storage and
+    the 2-byte chain built on it are refused."""
+
+    def __init__(self, model_name, n_class, pretrained=True, input_ch=6, ver="ver1"):
+        super().__init__()
+        if input_ch != 6:
+            raise ValueError("FuseDRNSegBase takes input_ch == 6 (RGB + HHA): its shared stem has 3 input channels and sees the HHA "
+                             "channels too, got input_ch = %r" % (input_ch,))
+        if ver != "ver1":
+            raise NotImplementedError("FuseDRNSegBase has no ver2 form (the reference looks up a constructor that does not exist)")
+        ctor = drn.__dict__.get(model_name)
+        if ctor is None or not model_name.startswith("drn_"):
+            raise NotImplementedError("unknown DRN variant %r" % (model_name,))
+        if not model_name.startswith("drn_d_"):
+            raise NotImplementedError("FuseDRNSegBase is built on the DRN-D trunks only (the reference asserts arch == \"D\"), got %r"
+                                      % (model_name,))
+        self.ver = ver
+        model = ctor(pretrained=pretrained, num_classes=0, input_ch=3)
+        sub_model = ctor(pretrained=pretrained, num_classes=0, input_ch=input_ch - 3)
+        for prefix, trunk in (("main", model), ("sub", sub_model)):
+            for k in range(9):
+                stage = getattr(trunk, "layer%d" % k)
+                if stage is None:
+                    raise NotImplementedError("%s has no layer%d: the FuseNet-style generator needs all nine stages" % (model_name, k))
+                setattr(self, "%s_layer%d" % (prefix, k), stage)
+        for k in range(9):
+            for p in getattr(self, "sub_layer%d" % k).parameters():
+                p.requires_grad_(False)
+        self.seg = _seg_head(model.out_dim, n_class)
+
+    def forward(self, x):
+        if ops.ACT_STORAGE == "compact":
+            raise NotImplementedError("FuseDRNSegBase hands out the fp32 outputs of its stages: it does not "
+                                      "run with MCDSEG_ACT_STORAGE=compact (nor the 2-byte chain built on it); use fp32 storage")
+        rgb, depth = x[:, :3, :, :], x[:, 3:, :, :]
+        stages = [getattr(self, "main_layer%d" % k) for k in range(9)]
+        # (one _LateGrad alias per weight: the HHA pass, which comes first, takes it, the RGB pass hands autograd the parameter itself --
+        # its weight gradient stays on the main stream and both reach p.grad by the end of the backward pass, ops._take_late)
+        with ops.late_weight_grads(self):
+            x_d = []
+            for stage in stages:
+                depth = _walk_stage(stage, depth)
+                x_d.append(depth)
+            x = rgb
+            for stage, x_dk in zip(stages, x_d):
+                x = ops.stage_join(_walk_stage(stage, x), x_dk)
+        return self.seg(x)
 
 
 class DRNSegPixelClassifier(nn.Module):

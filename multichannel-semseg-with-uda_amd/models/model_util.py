@@ -54,13 +54,22 @@ def get_full_uncertain_model(net, res, n_class, input_ch, criterion, is_data_par
 
 
 def get_models(net_name, input_ch, n_class, res="50", method="MCD", is_data_parallel=False):
-    if "drn" not in net_name or "fusenet" in net_name:
+    if "drn" not in net_name:
         raise NotImplementedError("Only FCN (Including Dilated FCN), SegNet, PSPNet UNet are supported!")
-    from models.dilated_fcn import (DRNSegBase, DRNSegPixelClassifier, FusionDRNSegPixelClassifier,
+    from models.dilated_fcn import (DRNSegBase, DRNSegPixelClassifier, FuseDRNSegBase, FusionDRNSegPixelClassifier,
                                     ScoreFusionDRNSegPixelClassifier)
     ver = "ver2" if "ver2" in net_name else "ver1"
     drn_name = net_name.replace("_ver2", "")
     pre = _pretrained_default()
+    if "fusenet" in net_name:
+        # middle fusion (models/model_util.py:187-195): one siamese DRN-D generator on RGB and HHA, the plain classifiers
+        if method != "MCD":
+            raise NotImplementedError("the FuseNet-style generator (%s) is built for method \"MCD\" only, got %r" % (net_name, method))
+        if ver == "ver2":
+            raise NotImplementedError("%s: there is no ver2 FuseNet-style generator (the reference looks up a constructor that does "
+                                      "not exist)" % net_name)
+        model_g = FuseDRNSegBase(model_name=drn_name.replace("_fusenet", ""), n_class=n_class, input_ch=input_ch, pretrained=pre)
+        return _wrap([model_g, DRNSegPixelClassifier(n_class=n_class), DRNSegPixelClassifier(n_class=n_class)], is_data_parallel)
     if method == "MCD":
         model_list = [DRNSegBase(model_name=drn_name, n_class=n_class, input_ch=input_ch, ver=ver, pretrained=pre),
                       DRNSegPixelClassifier(n_class=n_class, ver=ver), DRNSegPixelClassifier(n_class=n_class, ver=ver)]
