@@ -1390,7 +1390,7 @@ class _ConvBNAct(torch.autograd.Function):
             res_bound = _bound_or_measure(residual, res_bound)
         if training:
             track = call.running_mean is not None
-            ws = torch.empty(L.mcdseg_bn_stats_workspace_bytes(rows, c) // 8 + 1, dtype=torch.float64, device=z.device)
+            ws = _ws64(L.mcdseg_bn_stats_workspace_bytes(rows, c), z.device)
             with _timed("bn_stats_finalize", (0, 12 * rows * mpf)):  # (one launch also when it stands for BN_RUNNING_REPEAT forward passes)
                 check(L.mcdseg_bn_stats_finalize(_p(part), rows, c, mpf, _p(mean), _p(rstd), _p(call.running_mean) if track else None,
                                                  _p(call.running_var) if track else None, _p(call.nbt) if track else None,
@@ -2515,7 +2515,7 @@ class _ProbNLL(torch.autograd.Function):
             raise ValueError("mcdseg: labels %s do not match probabilities %s" % (tuple(labels.shape), tuple(p.shape)))
         loss = torch.empty(3, dtype=torch.float32, device=p.device)
         grad = torch.empty_like(p) if ctx.needs_input_grad[0] else None
-        ws = torch.empty(L.mcdseg_prob_nll_workspace_bytes(n, h * w) // 8 + 1, dtype=torch.float64, device=p.device)
+        ws = _ws64(L.mcdseg_prob_nll_workspace_bytes(n, h * w), p.device)
         check(L.mcdseg_prob_nll(_p(p), _p(labels), _p(weight), int(ignore_index), int(bool(size_average)), _p(grad), _p(loss), n, c,
                                 h * w, _p(ws), ctypes.c_size_t(ws.numel() * 8), _stream()), "prob_nll")
         ctx.g = grad
@@ -2568,7 +2568,7 @@ def resize_u8(src, out_wh, nearest=False):
         n, h, w, c = src.shape
     if (ow, oh) == (w, h):
         return src
-    ws = torch.empty(L.mcdseg_resize_workspace_bytes(n, h, w, c, oh, ow) // 4 + 2, dtype=torch.int32, device=src.device)
+    ws = _ws(L.mcdseg_resize_workspace_bytes(n, h, w, c, oh, ow), src.device)
     if nearest:
         dst = torch.empty((n, oh, ow), dtype=torch.uint8, device=src.device)
         check(L.mcdseg_resize_nearest_u8(_p(src), _p(dst), n, h, w, oh, ow, _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()),
