@@ -115,9 +115,11 @@ int64_t mcdseg_conv_split_stat_rows(const mcdseg_conv_desc* d);
 /* The thin full-resolution 3x3 layers (16 contraction channels, 16 / 32 outputs; models/drn.py:195-205 "_make_conv_layers") run,
  * with MCDSEG_MATH_F16X3 and a pre-split operand, on an LDS-window kernel whose partial-statistics rows differ (one per tile of
  * 8 (4) x 32 pixels and wave): mcdseg_conv_split_stat_rows_for gives the row count mcdseg_conv_split_fprop will write for this
- * (math, x_cb != NULL) combination; mcdseg_conv_split_window_ok tells whether that kernel takes the forward (dgrad = 0) or the
- * data gradient (dgrad = 1, stride 1 only).  It has no bias / affine epilogue: calling mcdseg_conv_split_fprop with a companion AND a
- * bias for such a geometry is rejected. */
+ * (math, x_cb != NULL) combination in a call WITHOUT bias / affine epilogue; mcdseg_conv_split_window_ok tells whether that kernel
+ * takes the forward (dgrad = 0) or the data gradient (dgrad = 1, stride 1 only).  It has no bias / affine epilogue: calling
+ * mcdseg_conv_split_fprop with a companion AND a bias for such a geometry is rejected -- and so is, with stat_partials, the stem with
+ * a companion and a bias, which the direct kernel would run with ITS row count (mcdseg_conv_split_stat_rows).  The entry points and
+ * these queries read one route (csrc/conv_gemm_split.hip, conv_route): a query's answer is a field of what the launch switches on. */
 int64_t mcdseg_conv_split_stat_rows_for(const mcdseg_conv_desc* d, int32_t math, int32_t presplit);
 int32_t mcdseg_conv_split_window_ok(const mcdseg_conv_desc* d, int32_t math, int32_t presplit, int32_t dgrad);
 /* Workgroup tile mcdseg_conv_split_fprop / _dgrad take for M output rows (Cout forward, Cin for the data gradient) and P output
@@ -188,14 +190,18 @@ int mcdseg_conv_split_wgrad(const mcdseg_conv_desc* d, int32_t math, const float
  * pre-split companions (register-transposing for bf16x6, transposed-read 128x128, transposed-read 256x128), 14 the 64-channel tap pairs,
  * 15 the thin-layer window kernel, 16 retired (two taps per workgroup), 17 the eight-wave ping-pong kernel over a stream-K decomposition
  * (256-channel blocks on both sides; csrc/conv_wgrad_split_pp.hip), 18 its row-of-taps form for 3 x KH kernels with at most 128
- * channels on one side (tiles of 128 co x three taps x 128 ci).  For profilers and bench.py's per-kernel accounting. */
+ * channels on one side (tiles of 128 co x three taps x 128 ci).  `presplit`: both companions (and the bound scalars the arithmetic
+ * needs) are passed.  This is what callers plan with -- which operands to keep, where to cut a batch, the kernel name a profiler will
+ * see -- and what the entry points themselves switch on (csrc/conv_wgrad.hip, wgrad_route). */
 int32_t mcdseg_conv_wgrad_variant(const mcdseg_conv_desc* d, int32_t math, int32_t presplit);
 /* 1 when ONE launch of mcdseg_conv_wgrad (math = 0) / mcdseg_conv_split_wgrad (presplit: both companions are passed) can address
  * this descriptor's operands with its 32-bit buffer offsets: (N*C + 128 channels of slack) planes below 2 GiB for the kernels that
  * read the fp32 tensors, N*C planes for the plans that read the companions (variants 11..18).  The host cuts larger batches along
  * N -- the reference has no such limit (nn.Conv2d, models/drn.py:21-23).  Host-side arithmetic, no launch. */
 int32_t mcdseg_conv_wgrad_fits(const mcdseg_conv_desc* d, int32_t math, int32_t presplit);
-/* dw = x (*) dy ; split over pixels into slabs in `workspace`, then reduced in a fixed order. */
+/* dw = x (*) dy ; split over pixels into slabs in `workspace`, then reduced in a fixed order.  mcdseg_conv_wgrad_workspace_bytes
+ * covers every call a caller may make for this descriptor under the current options: the largest need over mcdseg_conv_wgrad and
+ * mcdseg_conv_split_wgrad in each arithmetic, with and without the companions (and variant 15's whether or not its option is on). */
 size_t mcdseg_conv_wgrad_workspace_bytes(const mcdseg_conv_desc* d);
 int mcdseg_conv_wgrad(const mcdseg_conv_desc* d, const float* x, const float* dy, float* dw,
                       void* workspace, size_t workspace_bytes, void* stream);

@@ -960,8 +960,8 @@ int tile_config(int M, int64_t P, bool presplit) {
 }
 
 template <class P, bool DGRAD>
-void launch(const ConvSplitParams& p, int64_t pix0, hipStream_t st) {
-  switch (tile_config(p.M, p.P, p.src_cb != nullptr)) {  // (of the WHOLE problem, whatever the ping-pong kernel has taken: one row numbering)
+void launch(const ConvSplitParams& p, int tile, int64_t pix0, hipStream_t st) {
+  switch (tile) {  // (tile_config of the WHOLE problem, whatever the ping-pong kernel has taken: one row numbering)
     case 4222: launch_cfg<P, 4, 2, 2, 2, DGRAD>(p, pix0, st); break;
     case 4214: launch_cfg<P, 4, 2, 1, 4, DGRAD>(p, pix0, st); break;
     case 2222: launch_cfg<P, 2, 2, 2, 2, DGRAD>(p, pix0, st); break;
@@ -972,34 +972,11 @@ void launch(const ConvSplitParams& p, int64_t pix0, hipStream_t st) {
 
 }  // namespace
 
-// the 8-wave ping-pong tile (conv_gemm_split_pp.hip) takes whole rounds of 256 x 256 tiles, the kernels of this file the rest
-int64_t mcdseg_internal_conv_pp_pixels(const ConvSplitParams& p, int math, bool dgrad);
-int mcdseg_internal_conv_pp_launch(const ConvSplitParams& p, int math, bool dgrad, int64_t pixels, hipStream_t st);
-int mcdseg_internal_conv_pp_rest(const ConvSplitParams& p, int math, bool dgrad);
-int mcdseg_internal_conv_pp_wide(const ConvSplitParams& p, int math, bool dgrad);
-int mcdseg_internal_conv_pp_deep(const ConvSplitParams& p, int math);
-int mcdseg_internal_conv_pp_rest_launch(const ConvSplitParams& p, int math, bool dgrad, int64_t pix0, hipStream_t st);
-
-namespace {
-
-// part 0: the whole convolution; 1: only the pixels of the ping-pong kernel; 2: only the rest (mcdseg_conv_split_parts)
-template <bool DGRAD>
-int launch_math(int math, const ConvSplitParams& p, int part, hipStream_t st) {
-  const int64_t pp = mcdseg_internal_conv_pp_pixels(p, math, DGRAD);
-  if (pp > 0 && part != 2)
-    if (int rc = mcdseg_internal_conv_pp_launch(p, math, DGRAD, pp, st)) return rc;
-  if (pp >= p.P || part == 1) return 0;
-  if (mcdseg_internal_conv_pp_rest(p, math, DGRAD)) return mcdseg_internal_conv_pp_rest_launch(p, math, DGRAD, pp, st);
-  if (math == MCDSEG_MATH_F16X3)
-    launch<SplitF16x3, DGRAD>(p, pp, st);
-  else if (math == MCDSEG_MATH_F16X1)
-    launch<SplitF16x1, DGRAD>(p, pp, st);  // the same operands, one term
-  else
-    launch<SplitBf16x6, DGRAD>(p, pp, st);
-  return 0;
-}
-
-}  // namespace
+// the 8-wave ping-pong tiles (conv_gemm_split_pp.hip) take whole rounds of 256 x 256 tiles or a whole convolution, the kernels of this
+// file the rest: the plan of one problem, and the two launches that are handed it
+ConvPpPlan mcdseg_internal_conv_pp_plan(const ConvSplitParams& p, int math, bool dgrad);
+int mcdseg_internal_conv_pp_launch(const ConvSplitParams& p, int math, bool dgrad, const ConvPpPlan& plan, hipStream_t st);
+int mcdseg_internal_conv_pp_rest_launch(const ConvSplitParams& p, int math, bool dgrad, const ConvPpPlan& plan, hipStream_t st);
 
 // direct convolution for the network stem (conv_stem_x6.hip; bf16x6 arithmetic whatever `math` says -- its operand is
 // the network input, which no producer pre-splits, and the layer is 0.5 % of the step)
@@ -1023,42 +1000,135 @@ static int64_t stem_image_offset(const mcdseg_conv_desc* d, int math) {
 
 extern "C" int32_t mcdseg_conv_split_direct_ok(const mcdseg_conv_desc* d) { return d != nullptr && mcdseg_internal_stem_ok(d) ? 1 : 0; }
 
-static int64_t stat_rows_of(const mcdseg_conv_desc* d, bool presplit) {
-  const int cfg = tile_config(d->Cout, (int64_t)d->N * d->Ho * d->Wo, presplit);
-  const int64_t waves_n = cfg % 10, bn = 32 * ((cfg / 100) % 10) * waves_n;  // pixel tile and column waves of launch<>
-  return ceil_div64((int64_t)d->N * d->Ho * d->Wo, bn) * waves_n;
+// BatchNorm partial rows of the 4-wave tiles: one per wave column of a pixel tile of launch<>
+static int64_t tile_stat_rows(int64_t P, int tile) {
+  const int64_t waves_n = tile % 10, bn = 32 * ((tile / 100) % 10) * waves_n;
+  return ceil_div64(P, bn) * waves_n;
 }
 
 extern "C" int64_t mcdseg_conv_split_stat_rows(const mcdseg_conv_desc* d) {
   if (d == nullptr) return -22;
   if (mcdseg_internal_stem_ok(d)) return mcdseg_internal_stem_stat_rows(d);
-  return stat_rows_of(d, false);
+  const int64_t P = (int64_t)d->N * d->Ho * d->Wo;
+  return tile_stat_rows(P, tile_config(d->Cout, P, false));
 }
 
-static int fill_fprop_params(const mcdseg_conv_desc* d, int math, const void* x_cb, ConvSplitParams& p);
+// one piece of the companion of this call's N images, and the distance between the pieces (the companion's own batch d->Ncb)
+// (F16X1 multiplies -- and therefore reads -- the leading piece only: its piece stride is 0, so that a companion stored as ONE piece,
+// the 2-byte activation storage of round 6, can never be read past its end by a kernel that addresses "piece 1")
+static int split_cb_bytes(const mcdseg_conv_desc* d, int math, int C, int HW, bool cb, int* piece_bytes, long long* piece_stride) {
+  *piece_bytes = 0;
+  *piece_stride = 0;
+  if (!cb) return 0;
+  MCD_REQUIRE((C % 8) == 0, "conv_split: a pre-split operand needs a channel count divisible by 8 (got %d)", C);
+  MCD_REQUIRE(d->Ncb == 0 || d->Ncb >= d->N, "conv_split: Ncb (%d) must be 0 or at least N (%d)", d->Ncb, d->N);
+  const int64_t b = (int64_t)d->N * C * HW * 2;
+  MCD_REQUIRE(b < (1ll << 31), "conv_split: one piece of the pre-split operand exceeds 2 GiB; split the batch");
+  *piece_bytes = (int)b;
+  *piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * C * HW * 2;
+  return 0;
+}
+
+// geometry of the implicit GEMM of one pass (everything but the data pointers): the forward pass gathers x (`cb`: its companion is
+// passed) for the pixels of y, the data gradient dy for the pixels of dx
+static int fill_params(const mcdseg_conv_desc* d, int math, bool dgrad, bool cb, ConvSplitParams& p) {
+  p.N = d->N;
+  p.Cs = dgrad ? d->Cout : d->Cin; p.Hs = dgrad ? d->Ho : d->H; p.Ws = dgrad ? d->Wo : d->W;
+  p.M = dgrad ? d->Cin : d->Cout; p.Hd = dgrad ? d->H : d->Ho; p.Wd = dgrad ? d->W : d->Wo;
+  if (int rc = split_cb_bytes(d, math, p.Cs, p.Hs * p.Ws, cb, &p.cb_bytes, &p.cb_piece_stride)) return rc;
+  p.Mp = mcd_mp(p.M);
+  p.Kp = round_up(p.Cs, 16);
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
+  p.P = d->N * p.Hd * p.Wd;
+  p.src_bytes = (int)((int64_t)d->N * p.Cs * p.Hs * p.Ws * 4);
+  const int64_t wb = split_image_bytes(math, p.M, p.Cs, d->KH * d->KW);
+  MCD_REQUIRE(wb < (1ll << 31), "conv_split_%s: packed weights exceed 2 GiB", dgrad ? "dgrad" : "fprop");
+  p.wp_bytes = (int)wb;
+  return 0;
+}
+
+// ---- One route per convolution pass: what mcdseg_conv_split_fprop / _dgrad launch for a call is decided HERE, once.  The entry points
+// switch on it, and the plan queries of mcdseg.h each return one of its fields -- for a call with the companion `presplit` says and a
+// plain epilogue -- so that what a caller sizes and names by is what the launch does.
+enum ConvRouteKind { ROUTE_STEM_DIRECT, ROUTE_WINDOW, ROUTE_GEMM };
+struct ConvRoute {
+  ConvRouteKind kind;  // the stem's direct kernel (conv_stem_x6.hip), the LDS-window kernel (conv_thin_window.hip), the implicit GEMM
+  ConvSplitParams p;   // ROUTE_GEMM: the kernels' parameters, all but the data pointers
+  ConvPpPlan pp;       // ROUTE_GEMM: what the ping-pong tiles take (nothing on the other routes)
+  int tile;            // ROUTE_GEMM: tile_config of the 4-wave kernels
+  int64_t stat_rows;   // forward: the BatchNorm partial rows the route writes
+};
+
+// `cb`: the gathered operand's companion is passed; `plain`: no bias and no affine epilogue.  The kind is always decided; the return
+// value is that of the implicit GEMM's parameter block (a companion it cannot address, a weight image past 2 GiB): the entry points
+// report it where they need the block, to the queries it means "no ping-pong plan".
+static int conv_route(const mcdseg_conv_desc* d, int math, bool dgrad, bool cb, bool plain, ConvRoute& r) {
+  r = ConvRoute{};
+  const bool window = mcd_storage_math(math) == MCDSEG_MATH_F16X3 && cb && mcdseg_internal_thin_window_ok(d, dgrad ? 1 : 0);
+  // the stem with a (zero-padded, 8-channel) companion of the network input runs on the window kernel; its fp32 form (and every
+  // bias / affine epilogue) on the direct bf16x6 kernel
+  if (!dgrad && mcdseg_internal_stem_ok(d) && !(window && plain)) {
+    r.kind = ROUTE_STEM_DIRECT;
+    r.stat_rows = mcdseg_internal_stem_stat_rows(d);
+    return 0;
+  }
+  if (window) {
+    r.kind = ROUTE_WINDOW;
+    r.stat_rows = dgrad ? 0 : mcdseg_internal_thin_window_stat_rows(d);
+    return 0;
+  }
+  r.kind = ROUTE_GEMM;
+  const int64_t P = (int64_t)d->N * (dgrad ? d->H * d->W : d->Ho * d->Wo);
+  r.tile = tile_config(dgrad ? d->Cin : d->Cout, P, cb);
+  const int rc = fill_params(d, math, dgrad, cb, r.p);
+  if (rc == 0) r.pp = mcdseg_internal_conv_pp_plan(r.p, math, dgrad);
+  if (dgrad) return rc;
+  if (r.pp.wide)  // the 256 / 128 x 320 tiles: one row per wave column of 160 pixels (256 x 160: its one wave column)
+    r.stat_rows = r.pp.wide == 3 ? ceil_div64(P, 160) : 2 * ceil_div64(P, 320);
+  else
+    r.stat_rows = tile_stat_rows(P, r.tile);
+  return rc;
+}
+
+// the route a plan query answers for: a call with (`presplit`) or without the companion, and a plain epilogue
+static ConvRoute query_route(const mcdseg_conv_desc* d, int32_t math, int32_t presplit, int32_t dgrad) {
+  ConvRoute r;
+  (void)conv_route(d, math, dgrad != 0, presplit != 0, true, r);
+  return r;
+}
+
+namespace {
+
+// part 0: the whole convolution; 1: only the pixels of the ping-pong kernel; 2: only the rest (mcdseg_conv_split_parts)
+template <bool DGRAD>
+int launch_route(int math, const ConvRoute& r, int part, hipStream_t st) {
+  const ConvSplitParams& p = r.p;
+  const int64_t pp = r.pp.pixels;
+  if (pp > 0 && part != 2)
+    if (int rc = mcdseg_internal_conv_pp_launch(p, math, DGRAD, r.pp, st)) return rc;
+  if (pp >= p.P || part == 1) return 0;
+  if (r.pp.rest) return mcdseg_internal_conv_pp_rest_launch(p, math, DGRAD, r.pp, st);
+  if (math == MCDSEG_MATH_F16X3)
+    launch<SplitF16x3, DGRAD>(p, r.tile, pp, st);
+  else if (math == MCDSEG_MATH_F16X1)
+    launch<SplitF16x1, DGRAD>(p, r.tile, pp, st);  // the same operands, one term
+  else
+    launch<SplitBf16x6, DGRAD>(p, r.tile, pp, st);
+  return 0;
+}
+
+}  // namespace
 
 extern "C" int64_t mcdseg_conv_split_stat_rows_for(const mcdseg_conv_desc* d, int32_t math, int32_t presplit) {
-  math = mcd_storage_math(math);  // F16X1 shares F16X3's storage
   if (d == nullptr) return -22;
-  if (math == MCDSEG_MATH_F16X3 && presplit && mcdseg_internal_thin_window_ok(d, 0)) return mcdseg_internal_thin_window_stat_rows(d);
-  if (mcdseg_internal_stem_ok(d)) return mcdseg_internal_stem_stat_rows(d);
-  if (presplit) {  // the 256 x 320 ping-pong tile: one row per wave column of 160 pixels
-    ConvSplitParams p;
-    if (fill_fprop_params(d, math, d, p) == 0) {
-      const int kind = mcdseg_internal_conv_pp_wide(p, math, false);
-      if (kind == 3) return ceil_div64((int64_t)d->N * d->Ho * d->Wo, 160);  // (256 x 160: one wave column)
-      if (kind) return 2 * ceil_div64((int64_t)d->N * d->Ho * d->Wo, 320);
-    }
-  }
-  return stat_rows_of(d, presplit != 0);
+  return query_route(d, math, presplit, 0).stat_rows;
 }
 
 extern "C" int32_t mcdseg_conv_split_tile_config(int32_t M, int64_t P, int32_t presplit) { return tile_config(M, P, presplit != 0); }
 
 // 1 when mcdseg_conv_split_fprop / _dgrad run this geometry on the LDS-window kernel (for profilers and the benchmark's accounting)
 extern "C" int32_t mcdseg_conv_split_window_ok(const mcdseg_conv_desc* d, int32_t math, int32_t presplit, int32_t dgrad) {
-  math = mcd_storage_math(math);  // F16X1 shares F16X3's storage
-  return d != nullptr && math == MCDSEG_MATH_F16X3 && presplit && mcdseg_internal_thin_window_ok(d, dgrad) ? 1 : 0;
+  return d != nullptr && query_route(d, math, presplit, dgrad).kind == ROUTE_WINDOW ? 1 : 0;
 }
 
 extern "C" int mcdseg_absmax(const float* x, int64_t n, float* bound, void* stream) {
@@ -1139,24 +1209,6 @@ extern "C" int mcdseg_conv_split_pack_weights_multi(const int64_t* ptrs, const i
   return 0;
 }
 
-// one piece of the companion of this call's N images, and the distance between the pieces (the companion's own batch d->Ncb)
-// (F16X1 multiplies -- and therefore reads -- the leading piece only: its piece stride is 0, so that a companion stored as ONE piece,
-// the 2-byte activation storage of round 6, can never be read past its end by a kernel that addresses "piece 1")
-static int split_cb_bytes(const mcdseg_conv_desc* d, int math, int C, int HW, const void* cb, int* piece_bytes, long long* piece_stride) {
-  *piece_bytes = 0;
-  *piece_stride = 0;
-  if (cb == nullptr) return 0;
-  MCD_REQUIRE((C % 8) == 0, "conv_split: a pre-split operand needs a channel count divisible by 8 (got %d)", C);
-  MCD_REQUIRE(d->Ncb == 0 || d->Ncb >= d->N, "conv_split: Ncb (%d) must be 0 or at least N (%d)", d->Ncb, d->N);
-  const int64_t b = (int64_t)d->N * C * HW * 2;
-  MCD_REQUIRE(b < (1ll << 31), "conv_split: one piece of the pre-split operand exceeds 2 GiB; split the batch");
-  *piece_bytes = (int)b;
-  *piece_stride = math == MCDSEG_MATH_F16X1 ? 0 : (long long)(d->Ncb ? d->Ncb : d->N) * C * HW * 2;
-  return 0;
-}
-
-static int fill_fprop_params(const mcdseg_conv_desc* d, int math, const void* x_cb, ConvSplitParams& p);
-
 static int split_fprop_impl(const mcdseg_conv_desc* d, int math, const float* x, const void* x_cb, const float* x_bound, const void* wp,
                             const float* w_bound, const float* bias, float* y, float* stats, const float* ep_scale,
                             const float* ep_shift, const float* ep_res, int ep_relu, void* stream, int part = 0, void* z16 = nullptr,
@@ -1169,54 +1221,37 @@ static int split_fprop_impl(const mcdseg_conv_desc* d, int math, const float* x,
                 "to write and no bias / affine epilogue (mcdseg_conv_split_half_ok tells)");
     MCD_REQUIRE((int64_t)d->N * d->Cout * d->Ho * d->Wo * 2 < (1ll << 32), "conv_split_fprop_half: output above 4 GiB; split the batch");
   }
-  const bool stem = mcdseg_internal_stem_ok(d);
-  // the stem with a (zero-padded, 8-channel) companion of the network input runs on the window kernel; its fp32 form (and every
-  // bias / affine epilogue) on the direct bf16x6 kernel
-  const int smath = mcd_storage_math(math);
-  const bool stem_window = stem && smath == MCDSEG_MATH_F16X3 && x_cb != nullptr && bias == nullptr && ep_scale == nullptr &&
-                           mcdseg_internal_thin_window_ok(d, 0);
-  if (part == 1 && (stem || (smath == MCDSEG_MATH_F16X3 && x_cb != nullptr && mcdseg_internal_thin_window_ok(d, 0)))) return 0;  // (no ping-pong part)
-  if (stem && !stem_window) {
+  const bool plain = bias == nullptr && ep_scale == nullptr;
+  ConvRoute r;
+  const int route_rc = conv_route(d, math, false, x_cb != nullptr, plain, r);
+  if (stats != nullptr && !plain) {  // `stats` was sized by mcdseg_conv_split_stat_rows_for, which answers for a plain epilogue
+    const int64_t asked = query_route(d, math, x_cb != nullptr, 0).stat_rows;
+    MCD_REQUIRE(asked == r.stat_rows,
+                "conv_split_fprop: with a bias / affine epilogue this call writes %lld partial-statistics rows, not the %lld that "
+                "mcdseg_conv_split_stat_rows_for answers; pass no companion or no stat_partials",
+                (long long)r.stat_rows, (long long)asked);
+  }
+  if (part == 1 && r.kind != ROUTE_GEMM) return 0;  // (no ping-pong part)
+  if (r.kind == ROUTE_STEM_DIRECT) {
     MCD_REQUIRE(x != nullptr, "conv_split_fprop: the stem kernel reads the fp32 input");
     return mcdseg_internal_stem_fprop(d, x, (const char*)wp + stem_image_offset(d, math), bias, y, stats, ep_scale, ep_shift, ep_res,
                                       ep_relu, (hipStream_t)stream);
   }
-  MCD_REQUIRE(smath != MCDSEG_MATH_F16X3 || (x_bound && w_bound), "conv_split_fprop: f16x3 needs the operand and weight bound scalars");
-  if (smath == MCDSEG_MATH_F16X3 && x_cb != nullptr && mcdseg_internal_thin_window_ok(d, 0)) {
+  MCD_REQUIRE(mcd_storage_math(math) != MCDSEG_MATH_F16X3 || (x_bound && w_bound), "conv_split_fprop: f16x3 needs the operand and weight bound scalars");
+  if (r.kind == ROUTE_WINDOW) {
     // the window kernel has no bias / affine epilogue: those callers (conv+bias heads, folded-BN inference) have no companion
-    MCD_REQUIRE(bias == nullptr && ep_scale == nullptr, "conv_split_fprop: the thin-layer window kernel takes no bias / affine epilogue");
+    MCD_REQUIRE(plain, "conv_split_fprop: the thin-layer window kernel takes no bias / affine epilogue");
     return mcdseg_internal_thin_window_launch(d, 0, x_cb, x_bound, wp, split_image_bytes(math, d->Cout, d->Cin, d->KH * d->KW), w_bound, y,
                                               stats, (hipStream_t)stream);
   }
-  ConvSplitParams p;
-  if (int rc = fill_fprop_params(d, math, x_cb, p)) return rc;
-  p.src_bound = x_bound; p.w_bound = w_bound;
+  if (route_rc) return route_rc;
+  ConvSplitParams& p = r.p;  // (every field conv_route does not fill is zero)
+  p.src_cb = x_cb; p.src_bound = x_bound; p.w_bound = w_bound;
   p.src = x; p.wp = wp; p.bias = bias; p.dst = y; p.stats = stats;
   p.ep_scale = ep_scale; p.ep_shift = ep_shift; p.ep_res = ep_res; p.ep_relu = ep_relu;
   p.dst16 = z16; p.dst_bound = z_bound;
-  if (int rc = launch_math<false>(math, p, part, (hipStream_t)stream)) return rc;
+  if (int rc = launch_route<false>(math, r, part, (hipStream_t)stream)) return rc;
   MCD_LAUNCH_CHECK("conv_split_fprop");
-  return 0;
-}
-
-// geometry of the forward implicit GEMM (everything but the data pointers)
-static int fill_fprop_params(const mcdseg_conv_desc* d, int math, const void* x_cb, ConvSplitParams& p) {
-  if (int rc = split_cb_bytes(d, math, d->Cin, d->H * d->W, x_cb, &p.cb_bytes, &p.cb_piece_stride)) return rc;
-  p.src_cb = x_cb;
-  p.N = d->N;
-  p.Cs = d->Cin; p.Hs = d->H; p.Ws = d->W;
-  p.M = d->Cout; p.Hd = d->Ho; p.Wd = d->Wo;
-  p.Mp = mcd_mp(d->Cout);
-  p.Kp = round_up(d->Cin, 16);
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.P = d->N * d->Ho * d->Wo;
-  p.src_bytes = (int)((int64_t)d->N * d->Cin * d->H * d->W * 4);
-  const int64_t wb = split_image_bytes(math, d->Cout, d->Cin, d->KH * d->KW);
-  MCD_REQUIRE(wb < (1ll << 31), "conv_split_fprop: packed weights exceed 2 GiB");
-  p.wp_bytes = (int)wb;
-  p.sub = 0; p.tile_n0 = 0; p.tile_n1 = 0;
-  p.ep_res_lds = 0; p.ep_res_bytes = 0;
-  p.dst16 = nullptr; p.dst_bound = nullptr; p.ep_res16 = nullptr;
   return 0;
 }
 
@@ -1233,26 +1268,6 @@ extern "C" int mcdseg_conv_split_fprop_affine(const mcdseg_conv_desc* d, int32_t
   return split_fprop_impl(d, math, x, x_cb, x_bound, wp_fprop, w_bound, nullptr, y, nullptr, scale, shift, residual, relu, stream);
 }
 
-static int fill_dgrad_params(const mcdseg_conv_desc* d, int math, const void* dy_cb, ConvSplitParams& p) {
-  if (int rc = split_cb_bytes(d, math, d->Cout, d->Ho * d->Wo, dy_cb, &p.cb_bytes, &p.cb_piece_stride)) return rc;
-  p.src_cb = dy_cb;
-  p.N = d->N;
-  p.Cs = d->Cout; p.Hs = d->Ho; p.Ws = d->Wo;
-  p.M = d->Cin; p.Hd = d->H; p.Wd = d->W;
-  p.Mp = mcd_mp(d->Cin);
-  p.Kp = round_up(d->Cout, 16);
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.P = d->N * d->H * d->W;
-  p.src_bytes = (int)((int64_t)d->N * d->Cout * d->Ho * d->Wo * 4);
-  const int64_t wb = split_image_bytes(math, d->Cin, d->Cout, d->KH * d->KW);
-  MCD_REQUIRE(wb < (1ll << 31), "conv_split_dgrad: packed weights exceed 2 GiB");
-  p.wp_bytes = (int)wb;
-  p.sub = 0; p.tile_n0 = 0; p.tile_n1 = 0;
-  p.ep_res_lds = 0; p.ep_res_bytes = 0;
-  p.dst16 = nullptr; p.dst_bound = nullptr; p.ep_res16 = nullptr;
-  return 0;
-}
-
 static int split_dgrad_impl(const mcdseg_conv_desc* d, int32_t math, const float* dy, const void* dy_cb, const float* dy_bound,
                             const void* wp_dgrad, const float* w_bound, float* dx, void* stream, int part, const float* addend = nullptr,
                             void* dx16 = nullptr, const void* addend16 = nullptr) {
@@ -1264,19 +1279,19 @@ static int split_dgrad_impl(const mcdseg_conv_desc* d, int32_t math, const float
                 "(mcdseg_conv_split_half_ok tells)");
     MCD_REQUIRE((int64_t)d->N * d->Cin * d->H * d->W * 2 < (1ll << 32), "conv_split_dgrad_half: output above 4 GiB; split the batch");
   }
-  const int smath = mcd_storage_math(math);
-  MCD_REQUIRE(smath != MCDSEG_MATH_F16X3 || (dy_bound && w_bound), "conv_split_dgrad: f16x3 needs the operand and weight bound scalars");
-  MCD_REQUIRE(addend == nullptr || !(smath == MCDSEG_MATH_F16X3 && dy_cb != nullptr && mcdseg_internal_thin_window_ok(d, 1)),
+  ConvRoute r;
+  const int route_rc = conv_route(d, math, true, dy_cb != nullptr, true, r);
+  MCD_REQUIRE(mcd_storage_math(math) != MCDSEG_MATH_F16X3 || (dy_bound && w_bound), "conv_split_dgrad: f16x3 needs the operand and weight bound scalars");
+  MCD_REQUIRE(addend == nullptr || r.kind != ROUTE_WINDOW,
               "conv_split_dgrad_add: the thin-layer window kernel takes no addend (mcdseg_conv_split_window_ok tells)");
-  if (smath == MCDSEG_MATH_F16X3 && dy_cb != nullptr && mcdseg_internal_thin_window_ok(d, 1))
+  if (r.kind == ROUTE_WINDOW)
     return part == 1 ? 0
                      : mcdseg_internal_thin_window_launch(d, 1, dy_cb, dy_bound, wp_dgrad, split_image_bytes(math, d->Cin, d->Cout, d->KH * d->KW),
                                                           w_bound, dx, nullptr, (hipStream_t)stream);
-  ConvSplitParams p;
-  if (int rc = fill_dgrad_params(d, math, dy_cb, p)) return rc;
-  p.src_bound = dy_bound; p.w_bound = w_bound;
-  p.src = dy; p.wp = wp_dgrad; p.bias = nullptr; p.dst = dx; p.stats = nullptr;
-  p.ep_scale = nullptr; p.ep_shift = nullptr; p.ep_res = addend; p.ep_relu = 0;
+  if (route_rc) return route_rc;
+  ConvSplitParams& p = r.p;  // (every field conv_route does not fill is zero: no bias, no statistics, no affine epilogue)
+  p.src_cb = dy_cb; p.src_bound = dy_bound; p.w_bound = w_bound;
+  p.src = dy; p.wp = wp_dgrad; p.dst = dx; p.ep_res = addend;
   p.dst16 = dx16; p.ep_res16 = addend16;
   if (addend != nullptr) {
     const bool stage = mcd_opt(MCD_OPT_DGRAD_ADD_LDS) != 0;  // development knob
@@ -1284,7 +1299,7 @@ static int split_dgrad_impl(const mcdseg_conv_desc* d, int32_t math, const float
     p.ep_res_lds = stage && ((d->H * d->W) & 3) == 0 && (reinterpret_cast<uintptr_t>(addend) & 15) == 0 && bytes < (1ll << 32) ? 1 : 0;
     p.ep_res_bytes = (unsigned)(bytes < (1ll << 32) ? bytes : 0);
   }
-  if (int rc = launch_math<true>(math, p, part, (hipStream_t)stream)) return rc;
+  if (int rc = launch_route<true>(math, r, part, (hipStream_t)stream)) return rc;
   MCD_LAUNCH_CHECK("conv_split_dgrad");
   return 0;
 }
@@ -1308,35 +1323,21 @@ extern "C" int mcdseg_conv_split_dgrad_add(const mcdseg_conv_desc* d, int32_t ma
 // ---- the two launches of one convolution, separately (profilers and bench.py's per-kernel HIP events; results are those of the whole call)
 extern "C" int64_t mcdseg_conv_split_parts(const mcdseg_conv_desc* d, int32_t math, int32_t presplit, int32_t dgrad) {
   if (d == nullptr || !mcd_math_known(math) || !presplit) return 0;
-  const int smath = mcd_storage_math(math);
-  if (smath == MCDSEG_MATH_F16X3 && mcdseg_internal_thin_window_ok(d, dgrad ? 1 : 0)) return 0;
-  if (!dgrad && mcdseg_internal_stem_ok(d)) return 0;
-  ConvSplitParams p;
-  if (dgrad ? fill_dgrad_params(d, math, d, p) : fill_fprop_params(d, math, d, p)) return 0;
-  return mcdseg_internal_conv_pp_pixels(p, math, dgrad != 0);
+  return query_route(d, math, presplit, dgrad).pp.pixels;
 }
 
 // 1 when the launch that `part` 2 stands for (every pixel mcdseg_conv_split_parts does not give to the 256 x 256 tile) runs on the
 // 256 x 128 ping-pong tile, 0 when it runs on the 4-wave tiles (kernel names for profilers / bench.py)
 extern "C" int32_t mcdseg_conv_split_rest_pingpong(const mcdseg_conv_desc* d, int32_t math, int32_t presplit, int32_t dgrad) {
   if (d == nullptr || !mcd_math_known(math) || !presplit) return 0;
-  const int smath = mcd_storage_math(math);
-  if (smath == MCDSEG_MATH_F16X3 && mcdseg_internal_thin_window_ok(d, dgrad ? 1 : 0)) return 0;
-  if (!dgrad && mcdseg_internal_stem_ok(d)) return 0;
-  ConvSplitParams p;
-  if (dgrad ? fill_dgrad_params(d, math, d, p) : fill_fprop_params(d, math, d, p)) return 0;
-  return mcdseg_internal_conv_pp_rest(p, math, dgrad != 0);
+  return query_route(d, math, presplit, dgrad).pp.rest;
 }
 
-// 1 when the whole convolution runs on the 256 x 320 ping-pong tile (mcdseg_conv_split_parts then returns every pixel)
+// 1 when the whole convolution runs on the 256 x 320 ping-pong tile (mcdseg_conv_split_parts then returns every pixel); 2: 128 x 320
+// (output rows a multiple of 128 only); 3: 256 x 160
 extern "C" int32_t mcdseg_conv_split_wide_pingpong(const mcdseg_conv_desc* d, int32_t math, int32_t presplit, int32_t dgrad) {
   if (d == nullptr || !mcd_math_known(math) || !presplit) return 0;
-  const int smath = mcd_storage_math(math);
-  if (smath == MCDSEG_MATH_F16X3 && mcdseg_internal_thin_window_ok(d, dgrad ? 1 : 0)) return 0;
-  if (!dgrad && mcdseg_internal_stem_ok(d)) return 0;
-  ConvSplitParams p;
-  if (dgrad ? fill_dgrad_params(d, math, d, p) : fill_fprop_params(d, math, d, p)) return 0;
-  return mcdseg_internal_conv_pp_wide(p, math, dgrad != 0);  // 1: 256 x 320; 2: 128 x 320 (output rows a multiple of 128 only); 3: 256 x 160
+  return query_route(d, math, presplit, dgrad).pp.wide;
 }
 
 extern "C" int mcdseg_conv_split_fprop_part(const mcdseg_conv_desc* d, int32_t math, const float* x, const void* x_cb, const float* x_bound,
@@ -1362,8 +1363,7 @@ extern "C" int mcdseg_conv_split_dgrad_part(const mcdseg_conv_desc* d, int32_t m
 extern "C" int32_t mcdseg_conv_split_half_ok(const mcdseg_conv_desc* d, int32_t math, int32_t dgrad) {
   if (d == nullptr || math != MCDSEG_MATH_F16X1) return 0;
   if ((d->Cin & 7) != 0 || (d->Cout & 7) != 0 || (dgrad ? d->Cout : d->Cin) < 16) return 0;
-  if (mcdseg_internal_thin_window_ok(d, dgrad ? 1 : 0) || mcdseg_internal_stem_ok(d)) return 0;
-  return 1;
+  return query_route(d, math, 1, dgrad).kind == ROUTE_GEMM && !mcdseg_internal_stem_ok(d) ? 1 : 0;  // (nor the stem's data gradient)
 }
 
 extern "C" int mcdseg_conv_split_fprop_half(const mcdseg_conv_desc* d, int32_t math, const void* x_cb, const float* x_bound,
@@ -1387,7 +1387,5 @@ extern "C" int mcdseg_conv_split_dgrad_half(const mcdseg_conv_desc* d, int32_t m
 // rocprofv3 prints is then SplitF16x1D; the 256 x 128 tile never does)
 extern "C" int32_t mcdseg_conv_split_pp_deep(const mcdseg_conv_desc* d, int32_t math, int32_t dgrad) {
   if (d == nullptr || !mcd_math_known(math)) return 0;
-  ConvSplitParams p;
-  if (dgrad ? fill_dgrad_params(d, math, d, p) : fill_fprop_params(d, math, d, p)) return 0;
-  return mcdseg_internal_conv_pp_deep(p, math);
+  return query_route(d, math, 1, dgrad).pp.deep;
 }

@@ -16,7 +16,7 @@
 // workgroups): 0.594 of 2.5 PFLOP/s against 0.527 for the 4-wave structure; without the stagger the same 8-wave tile gets 0.44.
 //
 // One workgroup per CU (256 x 256: 96 KB of LDS, three stages of 16 + 16 KB), so a grid is worth whole rounds of CUs only.  The host
-// (pp_wide / mcdseg_internal_conv_pp_pixels below, called from conv_gemm_split.hip::launch_math) plans a convolution either as ONE
+// (pp_wide / mcdseg_internal_conv_pp_plan below, called from conv_gemm_split.hip::conv_route) plans a convolution either as ONE
 // launch of the 256 x 320 (128 x 320) tile -- whose width makes BASELINE config 2's 76800 pixels 0.94 of a round -- or as whole rounds of
 // 256 x 256 tiles plus the rest on 256 x 128 tiles, or leaves it to the 4-wave tiles.  K order, term order and the epilogue are those
 // of conv_gemm_split_kernel, so outputs are bit for bit the same whichever kernel computes a pixel, and so are the BatchNorm partial
@@ -576,7 +576,7 @@ int compute_units() {  // one workgroup per CU: a launch is worth whole rounds o
 int pp_mode() { return (int)mcd_opt(MCD_OPT_PINGPONG); }
 
 bool pp_applies(const ConvSplitParams& p, int math, bool dgrad, int bm = 256) {
-  if (p.src_cb == nullptr || mcd_math_pieces(math) != 2 || (p.Mp % bm) != 0) return false;
+  if (p.cb_bytes == 0 || mcd_math_pieces(math) != 2 || (p.Mp % bm) != 0) return false;  // (cb_bytes: 0 without a companion)
   return p.KH * p.KW <= 32 && !(dgrad && p.stride != 1) && (p.Cs & 7) == 0;
 }
 
@@ -652,7 +652,7 @@ int pp_wide(const ConvSplitParams& p, int math, bool dgrad) {
     const int64_t tiles_h = ceil_div64(p.P, 160) * m_tiles, rounds_h = ceil_div64(tiles_h, cus);
     return tiles_h * 100 >= fill * rounds_h * cus ? 3 : 0;
   }
-  int64_t n_pp = rounds * cus / m_tiles;  // (mcdseg_internal_conv_pp_pixels)
+  int64_t n_pp = rounds * cus / m_tiles;  // (mcdseg_internal_conv_pp_plan)
   if (n_pp > p.P / 256) n_pp = p.P / 256;
   const int64_t rest = ceil_div64(p.P - n_pp * 256, 128) * m_tiles;  // 256 x 128 workgroups
   // 4 x cost: hybrid = 4 rounds + 2 ceil(rest / CUs); wide = 5 rounds_w
@@ -672,64 +672,57 @@ int mcdseg_internal_device_cus() {
   return n;
 }
 
-// 1 when the whole convolution runs on the 256 x 320 ping-pong tile (BatchNorm partial rows of 160 pixels)
-int mcdseg_internal_conv_pp_wide(const ConvSplitParams& p, int math, bool dgrad) { return pp_wide(p, math, dgrad); }
-
-// 1 when the ping-pong launches of this problem (all but the 256 x 128 tile's) run as SplitF16x1D (kernel names for profilers)
-int mcdseg_internal_conv_pp_deep(const ConvSplitParams& p, int math) { return deep_applies<4, 2, 1, 4>(p, math) ? 1 : 0; }
-
-// Pixels (a multiple of 256, counted from pixel 0) of this problem that the 256 x 256 ping-pong tile takes: whole rounds of one tile
-// per CU; 0 when it does not apply (no pre-split operand, three-piece arithmetic, output rows not a multiple of 256, strided data
-// gradient, more than 32 taps, less than one round of tiles).
-int64_t mcdseg_internal_conv_pp_pixels(const ConvSplitParams& p, int math, bool dgrad) {
+// The ping-pong plan of one problem, decided once per call (conv_split_params.h):
+//   pixels  whole rounds of one 256 x 256 tile per CU, counted from pixel 0 -- none when the tile does not apply (no pre-split operand,
+//           three-piece arithmetic, output rows not a multiple of 256, strided data gradient, more than 32 taps) or makes less than one
+//           round (pp_min_rounds()); every pixel when the 256 x 320 tile takes the convolution (`wide`, BatchNorm partial rows of 160 pixels);
+//   rest    the pixels the 256 x 256 tile leaves (all of them when it takes none) run on the 256 x 128 ping-pong tile rather than on the
+//           4-wave tiles of conv_gemm_split.hip;
+//   deep    SplitF16x1D (kernel names for profilers).
+ConvPpPlan mcdseg_internal_conv_pp_plan(const ConvSplitParams& p, int math, bool dgrad) {
+  ConvPpPlan pl = {0, pp_wide(p, math, dgrad), 0, deep_applies<4, 2, 1, 4>(p, math) ? 1 : 0};
+  if (pl.wide) pl.pixels = p.P;
+  if (!pp_applies(p, math, dgrad)) return pl;
   const int mode = pp_mode();
-  if (pp_wide(p, math, dgrad)) return p.P;  // (everything, on the 256 x 320 tile)
-  if ((mode != 1 && mode != 3) || !pp_applies(p, math, dgrad)) return 0;
   const int64_t m_tiles = p.Mp / 256, n_full = p.P / 256, cus = compute_units();
   const int64_t rounds = n_full * m_tiles / cus;
-  if (rounds < 1 || rounds < pp_min_rounds()) return 0;
+  pl.rest = mode == 2 || (mode == 3 && rounds >= (pp_min_rounds() > 1 ? pp_min_rounds() : 1)) ? 1 : 0;
+  if (pl.wide || (mode != 1 && mode != 3) || rounds < 1 || rounds < pp_min_rounds()) return pl;
   int64_t n_pp = rounds * cus / m_tiles;  // pixel tiles (all their row tiles) that make whole rounds
   if (n_pp > n_full) n_pp = n_full;
-  return n_pp * 256;
+  pl.pixels = n_pp * 256;
+  return pl;
 }
 
-// 1 when the pixels the 256 x 256 tile leaves (all of them when it takes none) run on the 256 x 128 ping-pong tile rather than on the
-// 4-wave tiles of conv_gemm_split.hip
-int mcdseg_internal_conv_pp_rest(const ConvSplitParams& p, int math, bool dgrad) {
-  const int mode = pp_mode();
-  if (!pp_applies(p, math, dgrad)) return 0;
-  if (mode == 2) return 1;
-  return mode == 3 && (p.P / 256) * (p.Mp / 256) / compute_units() >= (pp_min_rounds() > 1 ? pp_min_rounds() : 1) ? 1 : 0;
-}
-
-int mcdseg_internal_conv_pp_launch(const ConvSplitParams& p, int math, bool dgrad, int64_t pixels, hipStream_t st) {
+// part 1 of the plan: plan.pixels on the 256 x 256 tile, or the whole convolution on the wide tile
+int mcdseg_internal_conv_pp_launch(const ConvSplitParams& p, int math, bool dgrad, const ConvPpPlan& plan, hipStream_t st) {
   ConvSplitParams q = p;
   q.sub = 0;
   q.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
   q.tile_n0 = 0;
-  if (const int kind = pp_wide(p, math, dgrad)) {
-    q.tile_n1 = ceil_div(p.P, kind == 3 ? 160 : 320);
-    if (kind == 1)
+  if (plan.wide) {
+    q.tile_n1 = ceil_div(p.P, plan.wide == 3 ? 160 : 320);
+    if (plan.wide == 1)
       launch_math<2, 5, 2, 2>(q, math, dgrad, st);
-    else if (kind == 2)
+    else if (plan.wide == 2)
       launch_math<1, 5, 2, 2>(q, math, dgrad, st);
     else
       launch_math<1, 5, 4, 1>(q, math, dgrad, st);
     MCD_LAUNCH_CHECK("conv_gemm_split_pp (256 / 128 x 320, 256 x 160)");
     return 0;
   }
-  q.tile_n1 = (int)(pixels / 256);
+  q.tile_n1 = (int)(plan.pixels / 256);
   launch_math<4, 2, 1, 4>(q, math, dgrad, st);
   MCD_LAUNCH_CHECK("conv_gemm_split_pp");
   return 0;
 }
 
-// the pixels from pix0 (a multiple of 256) to the end on the 256 x 128 ping-pong tile
-int mcdseg_internal_conv_pp_rest_launch(const ConvSplitParams& p, int math, bool dgrad, int64_t pix0, hipStream_t st) {
+// the pixels from plan.pixels (a multiple of 256) to the end on the 256 x 128 ping-pong tile
+int mcdseg_internal_conv_pp_rest_launch(const ConvSplitParams& p, int math, bool dgrad, const ConvPpPlan& plan, hipStream_t st) {
   ConvSplitParams q = p;
   q.sub = 0;
   q.skip_dead = mcd_opt(MCD_OPT_SKIP_DEAD_TAPS) != 0 ? 1 : 0;
-  q.tile_n0 = (int)(pix0 / 128);
+  q.tile_n0 = (int)(plan.pixels / 128);
   q.tile_n1 = ceil_div(p.P, 128);
   launch_math<2, 2, 2, 2>(q, math, dgrad, st);
   MCD_LAUNCH_CHECK("conv_gemm_split_pp (256 x 128)");

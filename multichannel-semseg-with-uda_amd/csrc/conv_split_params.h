@@ -50,5 +50,14 @@ struct ConvSplitParams {
   int skip_dead;
 };
 
+// What the ping-pong kernels take of one problem (host side; conv_gemm_split_pp.hip decides it once per call, the launchers of both
+// files and the plan queries of mcdseg.h read it)
+struct ConvPpPlan {
+  int64_t pixels;  // part 1: pixels from pixel 0 on the 256 x 256 tile (a multiple of 256), or every pixel when `wide`; 0: none
+  int wide;        // the whole problem as one launch of 1: the 256 x 320 tile, 2: its 128 x 320 form, 3: its 256 x 160 form; 0: no
+  int rest;        // 1: the pixels behind `pixels` run on the 256 x 128 ping-pong tile, 0: on the 4-wave tiles
+  int deep;        // 1: the ping-pong launches (all but the 256 x 128 tile's) run two K-steps per barrier interval (SplitF16x1D)
+};
+
 typedef _Float16 mcd_f16x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 mcd_bf16x4 __attribute__((ext_vector_type(4)));

@@ -481,35 +481,155 @@ int mcdseg_internal_wgrad_pp_launch(const mcdseg_conv_desc* d, int math, const v
 int mcdseg_internal_wgrad_pp3_plan(const mcdseg_conv_desc* d, int math, int* L, size_t* slab_floats, int* slabs = nullptr);
 int mcdseg_internal_wgrad_pp3_launch(const mcdseg_conv_desc* d, int math, const void* x_cb, const float* x_bound, const void* dy_cb,
                                      const float* dy_bound, float* dw, float* slab, hipStream_t st);
-static bool thin_tr_applies(const mcdseg_conv_desc* d, int math, const void* x_cb, const void* dy_cb) {
-  const bool on = mcd_opt(MCD_OPT_WGRAD_THIN_TR) != 0;
-  return on && mcd_storage_math(math) == MCDSEG_MATH_F16X3 && x_cb && dy_cb && mcdseg_internal_wgrad_thin_tr_ok(d);
+
+// ---- One route per weight gradient: which kernel mcdseg_conv_wgrad (math = 0) / mcdseg_conv_split_wgrad launch for a call is decided
+// HERE, once, from the descriptor, the arithmetic and what the call carries (`cb`: both companions, `bounds`: both bound scalars).
+// wgrad_impl switches on it; mcdseg_conv_wgrad_variant, _fits and _workspace_bytes answer from it.
+struct WgradRoute {
+  int code;            // the variant numbers of mcdseg_conv_wgrad_variant (include/mcdseg.h), 16 -- retired -- never
+  WgradPlan pl;        // the slab plan of variants 0..14
+  size_t slab_floats;  // workspace the variant needs
+  bool reads_cb;       // variants 11..18: both pre-split companions are its only operands
+};
+
+static WgradRoute wgrad_route(const mcdseg_conv_desc* d, int math, bool cb, bool bounds) {
+  WgradRoute r;
+  r.pl = make_plan(d);
+  const bool f16 = mcd_storage_math(math) == MCDSEG_MATH_F16X3, both8 = (d->Cin & 7) == 0 && (d->Cout & 7) == 0;
+  const bool pp = math && cb && bounds && r.pl.cfg == 0;  // the eight-wave ping-pong kernels, where they have a plan
+  size_t sf = 0;
+  // (options read per call: MCDSEG_WGRAD_THIN_TR=0 / MCDSEG_WGRAD_TR64=0 turn variants 15 / 14 off, tests)
+  if (cb && bounds && f16 && mcd_opt(MCD_OPT_WGRAD_THIN_TR) != 0 && mcdseg_internal_wgrad_thin_tr_ok(d))
+    r.code = 15;
+  else if (pp && mcdseg_internal_wgrad_pp_plan(d, math, nullptr, &sf) > 0)
+    r.code = 17;
+  else if (pp && mcdseg_internal_wgrad_pp3_plan(d, math, nullptr, &sf) > 0)
+    r.code = 18;
+  else if (cb && f16 && both8 && r.pl.cfg == 1 && mcd_opt(MCD_OPT_WGRAD_TR64) != 0)
+    r.code = 14;  // the 64 x 64 plan (32 < min(Cin, Cout) <= 64) from both pre-split companions: f16x3 only
+  else if (r.pl.cfg != 0 || math == 0)
+    r.code = r.pl.cfg;
+  else
+    r.code = cb && both8 ? 11 + mcdseg_internal_wgrad_cb_variant(d, math, r.pl.co_p, r.pl.ci_p, r.pl.splits) : 10;
+  r.slab_floats = r.code == 15 ? mcdseg_internal_wgrad_thin_tr_ws(d) / sizeof(float) : (r.code >= 17 ? sf : (size_t)r.pl.slab_floats);
+  r.reads_cb = r.code >= 11;
+  return r;
 }
 
-// the 64 x 64 plan (32 < min(Cin, Cout) <= 64) from both pre-split companions: f16x3 only (MCDSEG_WGRAD_TR64=0 turns it off)
-static bool tr64_applies(const mcdseg_conv_desc* d, int math, const void* x_cb, const void* dy_cb, int cfg) {
-  const bool on = mcd_opt(MCD_OPT_WGRAD_TR64) != 0;
-  return on && cfg == 1 && mcd_storage_math(math) == MCDSEG_MATH_F16X3 && x_cb && dy_cb && (d->Cin & 7) == 0 && (d->Cout & 7) == 0;
+// One launch addresses an operand with 32-bit buffer offsets.  The kernels that read the fp32 tensors express padding and ragged
+// channel tails as offsets up to a 128-channel tile past the tensor, which the buffer range check must still reject: (N*C + 128)
+// planes below 2 GiB.  The plans that read both pre-split companions (variants 11..18) mark such accesses with an explicit
+// out-of-range offset and check their own limits (one piece of a companion below 2 GiB): no slack.
+static bool wgrad_operands_fit(const mcdseg_conv_desc* d, const WgradRoute& r) {
+  const int64_t slack = r.reads_cb ? 0 : 128;
+  return ((int64_t)d->N * d->Cin + slack) * d->H * d->W * 4 < (1ll << 31) && ((int64_t)d->N * d->Cout + slack) * d->Ho * d->Wo * 4 < (1ll << 31);
+}
+
+// The kernel a call with (`presplit`) or without both companions, and with the bound scalars its arithmetic needs, runs on: what
+// callers plan storage, batch cuts and kernel names with (mcdseg/ops.py), profilers and the benchmark's per-kernel accounting
+extern "C" int32_t mcdseg_conv_wgrad_variant(const mcdseg_conv_desc* d, int32_t math, int32_t presplit) {
+  if (d == nullptr) return -22;
+  return wgrad_route(d, math, presplit != 0, true).code;
+}
+
+// 1 when ONE launch of mcdseg_conv_wgrad (math = 0) / mcdseg_conv_split_wgrad can address this descriptor's operands (presplit:
+// both companions are passed); the host cuts larger batches along N (mcdseg/ops.py::_batch_pieces).  Host-side arithmetic only.
+extern "C" int32_t mcdseg_conv_wgrad_fits(const mcdseg_conv_desc* d, int32_t math, int32_t presplit) {
+  if (d == nullptr || d->N <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->H <= 0 || d->W <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
+  return wgrad_operands_fit(d, wgrad_route(d, math, presplit != 0, true)) ? 1 : 0;
+}
+
+// the largest workspace of the routes a caller may take for this descriptor: every arithmetic, with and without the companions
+extern "C" size_t mcdseg_conv_wgrad_workspace_bytes(const mcdseg_conv_desc* d) {
+  if (d == nullptr) return 0;
+  size_t most = 0;
+  for (const int math : {0, MCDSEG_MATH_F16X3, MCDSEG_MATH_F16X1, MCDSEG_MATH_BF16X6})
+    for (int cb = 0; cb < 2; ++cb) {
+      const size_t need = wgrad_route(d, math, cb != 0, cb != 0).slab_floats * sizeof(float);
+      if (need > most) most = need;
+    }
+  const size_t thin = mcdseg_internal_wgrad_thin_tr_ws(d);  // (variant 15's also while option WGRAD_THIN_TR has it off: as always answered)
+  return most > thin ? most : thin;
 }
 
 static int wgrad_impl(const mcdseg_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
-                      int math, const void* x_cb, const float* x_bound, const void* dy_cb, const float* dy_bound, void* stream);
-
-// Which kernel mcdseg_conv_wgrad / mcdseg_conv_split_wgrad launch for this geometry (math = 0 for mcdseg_conv_wgrad):
-// 0..3 the f32 plans (128x128, 64x64, 32x32 tiles, tap-packed thin), 10 split arithmetic from fp32 operands, 11 / 12 / 13 / 14 from
-// both pre-split companions: register-transposing (bf16x6), transposed-read 128x128, transposed-read 256x128, transposed-read 64-channel
-// tap pairs, 15 the thin-layer window kernel, 16 retired (two taps per workgroup: measured slower and removed), 17 the eight-wave
-// ping-pong kernel (256 x 256 tiles), 18 its row-of-taps form for the 128-channel layers.  For profilers and the benchmark's per-kernel accounting; never needed to call the operators.
-extern "C" int32_t mcdseg_conv_wgrad_variant(const mcdseg_conv_desc* d, int32_t math, int32_t presplit) {
-  if (d == nullptr) return -22;
-  const WgradPlan pl = make_plan(d);
-  if (presplit && thin_tr_applies(d, math, d, d)) return 15;
-  if (presplit && math && pl.cfg == 0 && mcdseg_internal_wgrad_pp_plan(d, math, nullptr, nullptr) > 0) return 17;
-  if (presplit && math && pl.cfg == 0 && mcdseg_internal_wgrad_pp3_plan(d, math, nullptr, nullptr) > 0) return 18;
-  if (pl.cfg == 1 && presplit && tr64_applies(d, math, d, d, 1)) return 14;
-  if (pl.cfg != 0 || math == 0) return pl.cfg;
-  if (!(presplit && (d->Cin & 7) == 0 && (d->Cout & 7) == 0)) return 10;
-  return 11 + mcdseg_internal_wgrad_cb_variant(d, math, pl.co_p, pl.ci_p, pl.splits);
+                      int math, const void* x_cb, const float* x_bound, const void* dy_cb, const float* dy_bound, void* stream) {
+  MCD_REQUIRE(d && dw && workspace, "conv_wgrad: null pointer");
+  const WgradRoute r = wgrad_route(d, math, x_cb && dy_cb, x_bound && dy_bound);
+  const WgradPlan& pl = r.pl;
+  const size_t need = r.slab_floats * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  if (r.code == 15) return mcdseg_internal_wgrad_thin_tr_launch(d, x_cb, x_bound, dy_cb, dy_bound, dw, workspace, workspace_bytes, st);
+  if (r.code == 17 || r.code == 18) {
+    MCD_REQUIRE(workspace_bytes >= need, "conv_wgrad: workspace too small (%zu < %zu)", workspace_bytes, need);
+    return (r.code == 17 ? mcdseg_internal_wgrad_pp_launch : mcdseg_internal_wgrad_pp3_launch)(d, math, x_cb, x_bound, dy_cb, dy_bound, dw,
+                                                                                              (float*)workspace, st);
+  }
+  const bool scaled = r.code >= 10 && mcd_storage_math(math) == MCDSEG_MATH_F16X3;  // (the split plans' slab sums are in scaled units)
+  MCD_REQUIRE(!scaled || (x_bound && dy_bound), "conv_split_wgrad: f16x3 needs both bound scalars");
+  MCD_REQUIRE(r.reads_cb || (x && dy), "conv_wgrad: x and dy may be NULL only when the pre-split 128x128 plan applies");
+  MCD_REQUIRE(d->N > 0 && d->Cin > 0 && d->Cout > 0 && d->Ho > 0 && d->Wo > 0, "conv_wgrad: bad dims");
+  MCD_REQUIRE(wgrad_operands_fit(d, r),
+              "conv_wgrad: activation tensor must stay below 2 GiB (32-bit buffer offsets, plus a 128-channel tile of slack for the kernels "
+              "that read the fp32 operands); split the batch (mcdseg_conv_wgrad_fits)");
+  MCD_REQUIRE(workspace_bytes >= need, "conv_wgrad: workspace too small (%zu < %zu)", workspace_bytes, need);
+  const int T = d->KH * d->KW;
+  WgradParams p;
+  p.x = x; p.dy = dy; p.slab = (float*)workspace;
+  p.N = d->N; p.Cin = d->Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.Ho = d->Ho; p.Wo = d->Wo;
+  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
+  p.co_p = pl.co_p; p.ci_p = pl.ci_p; p.chunk = pl.chunk; p.chunks_per_img = pl.chunks_per_img; p.splits = pl.splits;
+  p.x_bytes = (int)((int64_t)d->N * d->Cin * d->H * d->W * 4);
+  p.dy_bytes = (int)((int64_t)d->N * d->Cout * d->Ho * d->Wo * 4);
+  p.groups = pl.groups;
+  const int64_t per_split = (int64_t)(pl.co_p / pl.bm) * (pl.ci_p / pl.bn) * pl.groups;
+  const int64_t nwg = 8 * ceil_div64(pl.splits, 8) * per_split;
+  MCD_REQUIRE(nwg < (1ll << 31), "conv_wgrad: grid too large");
+  dim3 grid((unsigned)nwg);
+  const int64_t total = (int64_t)T * d->Cout * d->Cin;
+  int rc = 0;
+  switch (r.code) {
+    case 3: {
+      const bool rows16 = d->Cout <= 16 && pl.co_p == 32;
+      if (pl.cinp == 8 && rows16)
+        hipLaunchKernelGGL((conv_wgrad_thin_kernel<8, true>), grid, dim3(64), 0, st, p);
+      else if (pl.cinp == 8)
+        hipLaunchKernelGGL((conv_wgrad_thin_kernel<8, false>), grid, dim3(64), 0, st, p);
+      else if (rows16)
+        hipLaunchKernelGGL((conv_wgrad_thin_kernel<16, true>), grid, dim3(64), 0, st, p);
+      else
+        hipLaunchKernelGGL((conv_wgrad_thin_kernel<16, false>), grid, dim3(64), 0, st, p);
+      MCD_LAUNCH_CHECK("conv_wgrad_thin");
+      hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, (const float*)workspace,
+                         dw, d->Cout, d->Cin, T, pl.co_p, pl.groups, pl.cinp, pl.splits);
+      MCD_LAUNCH_CHECK("conv_wgrad_thin_reduce");
+      return 0;
+    }
+    case 14:
+      rc = mcdseg_internal_wgrad_split_tr64_launch(d, math, x_cb, dy_cb, (float*)workspace, pl.co_p, pl.ci_p, pl.chunks_per_img, pl.splits, st);
+      break;
+    case 11: case 12: case 13:
+      rc = mcdseg_internal_wgrad_split_cb_launch(d, math, x_cb, dy_cb, (float*)workspace, pl.co_p, pl.ci_p, pl.chunks_per_img, pl.splits, st);
+      break;
+    case 10:
+      rc = mcdseg_internal_wgrad_split_launch(d, math, x, x_bound, dy, dy_bound, (float*)workspace, pl.co_p, pl.ci_p, pl.chunk,
+                                              pl.chunks_per_img, pl.splits, st);
+      break;
+    case 0: hipLaunchKernelGGL((conv_wgrad_kernel<2, 2, 2, 2, 16>), grid, dim3(256), 0, st, p); break;
+    case 1: hipLaunchKernelGGL((conv_wgrad_kernel<1, 1, 2, 2, 32>), grid, dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL((conv_wgrad_kernel<1, 1, 1, 1, 32>), grid, dim3(64), 0, st, p); break;
+  }
+  if (rc) return rc;
+  MCD_LAUNCH_CHECK("conv_wgrad");
+  const int64_t pairs_all = (int64_t)d->Cout * d->Cin;
+  int PB = T == 1 ? 256 : 64;
+  while (PB > 16 && pairs_all / PB < 512) PB >>= 1;  // small layers: more, smaller blocks
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div64((int64_t)d->Cout * d->Cin, PB)), dim3(256),
+                     (size_t)PB * T * sizeof(float), st, (const float*)workspace, dw,
+                     d->Cout, d->Cin, T, pl.co_p, pl.ci_p, pl.splits, PB, scaled ? x_bound : (const float*)nullptr,
+                     scaled ? dy_bound : (const float*)nullptr);
+  MCD_LAUNCH_CHECK("conv_wgrad_reduce");
+  return 0;
 }
 
 extern "C" int mcdseg_conv_wgrad(const mcdseg_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace,
@@ -524,127 +644,4 @@ extern "C" int mcdseg_conv_split_wgrad(const mcdseg_conv_desc* d, int32_t math, 
                                        size_t workspace_bytes, void* stream) {
   MCD_REQUIRE(mcd_math_known(math), "conv_split_wgrad: unknown math %d", math);
   return wgrad_impl(d, x, dy, dw, workspace, workspace_bytes, math, x_cb, x_bound, dy_cb, dy_bound, stream);
-}
-
-// One launch addresses an operand with 32-bit buffer offsets.  The kernels that read the fp32 tensors express padding and ragged
-// channel tails as offsets up to a 128-channel tile past the tensor, which the buffer range check must still reject: (N*C + 128)
-// planes below 2 GiB.  The plans that read both pre-split companions (variants 11..18) mark such accesses with an explicit
-// out-of-range offset and check their own limits (one piece of a companion below 2 GiB): no slack.
-static bool wgrad_reads_companions(const mcdseg_conv_desc* d, int math, bool have_cb) {
-  if (!math || !have_cb) return false;
-  if (thin_tr_applies(d, math, d, d)) return true;
-  const int cfg = make_plan(d).cfg;
-  return tr64_applies(d, math, d, d, cfg) || ((d->Cin & 7) == 0 && (d->Cout & 7) == 0 && cfg == 0);
-}
-static bool wgrad_operands_fit(const mcdseg_conv_desc* d, int math, bool have_cb) {
-  const int64_t slack = wgrad_reads_companions(d, math, have_cb) ? 0 : 128;
-  return ((int64_t)d->N * d->Cin + slack) * d->H * d->W * 4 < (1ll << 31) && ((int64_t)d->N * d->Cout + slack) * d->Ho * d->Wo * 4 < (1ll << 31);
-}
-
-// 1 when ONE launch of mcdseg_conv_wgrad (math = 0) / mcdseg_conv_split_wgrad can address this descriptor's operands (presplit:
-// both companions are passed); the host cuts larger batches along N (mcdseg/ops.py::_batch_pieces).  Host-side arithmetic only.
-extern "C" int32_t mcdseg_conv_wgrad_fits(const mcdseg_conv_desc* d, int32_t math, int32_t presplit) {
-  if (d == nullptr || d->N <= 0 || d->Cin <= 0 || d->Cout <= 0 || d->H <= 0 || d->W <= 0 || d->Ho <= 0 || d->Wo <= 0) return 0;
-  return wgrad_operands_fit(d, math, presplit != 0) ? 1 : 0;
-}
-
-extern "C" size_t mcdseg_conv_wgrad_workspace_bytes(const mcdseg_conv_desc* d) {
-  if (d == nullptr) return 0;
-  size_t a = (size_t)make_plan(d).slab_floats * sizeof(float), c = 0;
-  const size_t b = mcdseg_internal_wgrad_thin_tr_ws(d);
-  if (mcdseg_internal_wgrad_pp_plan(d, MCDSEG_MATH_F16X3, nullptr, &c) > 0 && c * sizeof(float) > a) a = c * sizeof(float);
-  c = 0;
-  if (make_plan(d).cfg == 0 && mcdseg_internal_wgrad_pp3_plan(d, MCDSEG_MATH_F16X3, nullptr, &c) > 0 && c * sizeof(float) > a) a = c * sizeof(float);
-  return a > b ? a : b;
-}
-
-static int wgrad_impl(const mcdseg_conv_desc* d, const float* x, const float* dy, float* dw, void* workspace, size_t workspace_bytes,
-                      int math, const void* x_cb, const float* x_bound, const void* dy_cb, const float* dy_bound, void* stream) {
-  MCD_REQUIRE(d && dw && workspace, "conv_wgrad: null pointer");
-  if (thin_tr_applies(d, math, x_cb, dy_cb) && x_bound && dy_bound)
-    return mcdseg_internal_wgrad_thin_tr_launch(d, x_cb, x_bound, dy_cb, dy_bound, dw, workspace, workspace_bytes, (hipStream_t)stream);
-  if (math && x_cb && dy_cb && x_bound && dy_bound && make_plan(d).cfg == 0) {
-    size_t sf = 0;
-    if (mcdseg_internal_wgrad_pp_plan(d, math, nullptr, &sf) > 0) {
-      MCD_REQUIRE(workspace_bytes >= sf * sizeof(float), "conv_wgrad: workspace too small (%zu < %zu)", workspace_bytes, sf * sizeof(float));
-      return mcdseg_internal_wgrad_pp_launch(d, math, x_cb, x_bound, dy_cb, dy_bound, dw, (float*)workspace, (hipStream_t)stream);
-    }
-    sf = 0;
-    if (mcdseg_internal_wgrad_pp3_plan(d, math, nullptr, &sf) > 0) {
-      MCD_REQUIRE(workspace_bytes >= sf * sizeof(float), "conv_wgrad: workspace too small (%zu < %zu)", workspace_bytes, sf * sizeof(float));
-      return mcdseg_internal_wgrad_pp3_launch(d, math, x_cb, x_bound, dy_cb, dy_bound, dw, (float*)workspace, (hipStream_t)stream);
-    }
-  }
-  const bool tr64 = tr64_applies(d, math, x_cb, dy_cb, make_plan(d).cfg);
-  const bool cb_path = tr64 || (math && x_cb && dy_cb && (d->Cin & 7) == 0 && (d->Cout & 7) == 0 && make_plan(d).cfg == 0);
-  const bool split_plan = tr64 || (math && make_plan(d).cfg == 0);
-  MCD_REQUIRE(!(split_plan && mcd_storage_math(math) == MCDSEG_MATH_F16X3) || (x_bound && dy_bound), "conv_split_wgrad: f16x3 needs both bound scalars");
-  MCD_REQUIRE(cb_path || (x && dy), "conv_wgrad: x and dy may be NULL only when the pre-split 128x128 plan applies");
-  MCD_REQUIRE(d->N > 0 && d->Cin > 0 && d->Cout > 0 && d->Ho > 0 && d->Wo > 0, "conv_wgrad: bad dims");
-  MCD_REQUIRE(wgrad_operands_fit(d, math, x_cb && dy_cb),
-              "conv_wgrad: activation tensor must stay below 2 GiB (32-bit buffer offsets, plus a 128-channel tile of slack for the kernels "
-              "that read the fp32 operands); split the batch (mcdseg_conv_wgrad_fits)");
-  const WgradPlan pl = make_plan(d);
-  MCD_REQUIRE(workspace_bytes >= (size_t)pl.slab_floats * sizeof(float), "conv_wgrad: workspace too small (%zu < %zu)",
-              workspace_bytes, (size_t)pl.slab_floats * sizeof(float));
-  const int T = d->KH * d->KW;
-  WgradParams p;
-  p.x = x; p.dy = dy; p.slab = (float*)workspace;
-  p.N = d->N; p.Cin = d->Cin; p.H = d->H; p.W = d->W; p.Cout = d->Cout; p.Ho = d->Ho; p.Wo = d->Wo;
-  p.KH = d->KH; p.KW = d->KW; p.stride = d->stride; p.pad = d->pad; p.dil = d->dil;
-  p.co_p = pl.co_p; p.ci_p = pl.ci_p; p.chunk = pl.chunk; p.chunks_per_img = pl.chunks_per_img; p.splits = pl.splits;
-  p.x_bytes = (int)((int64_t)d->N * d->Cin * d->H * d->W * 4);
-  p.dy_bytes = (int)((int64_t)d->N * d->Cout * d->Ho * d->Wo * 4);
-  p.groups = pl.groups;
-  const int64_t per_split = (int64_t)(pl.co_p / pl.bm) * (pl.ci_p / pl.bn) * pl.groups;
-  const int64_t nwg = 8 * ceil_div64(pl.splits, 8) * per_split;
-  MCD_REQUIRE(nwg < (1ll << 31), "conv_wgrad: grid too large");
-  dim3 grid((unsigned)nwg);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t total = (int64_t)T * d->Cout * d->Cin;
-  if (pl.cfg == 3) {
-    const bool rows16 = d->Cout <= 16 && pl.co_p == 32;
-    if (pl.cinp == 8 && rows16)
-      hipLaunchKernelGGL((conv_wgrad_thin_kernel<8, true>), grid, dim3(64), 0, st, p);
-    else if (pl.cinp == 8)
-      hipLaunchKernelGGL((conv_wgrad_thin_kernel<8, false>), grid, dim3(64), 0, st, p);
-    else if (rows16)
-      hipLaunchKernelGGL((conv_wgrad_thin_kernel<16, true>), grid, dim3(64), 0, st, p);
-    else
-      hipLaunchKernelGGL((conv_wgrad_thin_kernel<16, false>), grid, dim3(64), 0, st, p);
-    MCD_LAUNCH_CHECK("conv_wgrad_thin");
-    hipLaunchKernelGGL(wgrad_thin_reduce_kernel, dim3((unsigned)ceil_div64(total, 4)), dim3(256), 0, st, (const float*)workspace,
-                       dw, d->Cout, d->Cin, T, pl.co_p, pl.groups, pl.cinp, pl.splits);
-    MCD_LAUNCH_CHECK("conv_wgrad_thin_reduce");
-    return 0;
-  }
-  const bool scaled = split_plan && mcd_storage_math(math) == MCDSEG_MATH_F16X3;
-  if (tr64) {
-    if (int rc = mcdseg_internal_wgrad_split_tr64_launch(d, math, x_cb, dy_cb, (float*)workspace, pl.co_p, pl.ci_p, pl.chunks_per_img,
-                                                         pl.splits, st))
-      return rc;
-  } else if (cb_path) {
-    if (int rc = mcdseg_internal_wgrad_split_cb_launch(d, math, x_cb, dy_cb, (float*)workspace, pl.co_p, pl.ci_p, pl.chunks_per_img,
-                                                       pl.splits, st))
-      return rc;
-  } else if (pl.cfg == 0 && math) {
-    if (int rc = mcdseg_internal_wgrad_split_launch(d, math, x, x_bound, dy, dy_bound, (float*)workspace, pl.co_p, pl.ci_p, pl.chunk,
-                                                    pl.chunks_per_img, pl.splits, st))
-      return rc;
-  } else if (pl.cfg == 0)
-    hipLaunchKernelGGL((conv_wgrad_kernel<2, 2, 2, 2, 16>), grid, dim3(256), 0, st, p);
-  else if (pl.cfg == 1)
-    hipLaunchKernelGGL((conv_wgrad_kernel<1, 1, 2, 2, 32>), grid, dim3(256), 0, st, p);
-  else
-    hipLaunchKernelGGL((conv_wgrad_kernel<1, 1, 1, 1, 32>), grid, dim3(64), 0, st, p);
-  MCD_LAUNCH_CHECK("conv_wgrad");
-  const int64_t pairs_all = (int64_t)d->Cout * d->Cin;
-  int PB = T == 1 ? 256 : 64;
-  while (PB > 16 && pairs_all / PB < 512) PB >>= 1;  // small layers: more, smaller blocks
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)ceil_div64((int64_t)d->Cout * d->Cin, PB)), dim3(256),
-                     (size_t)PB * T * sizeof(float), st, (const float*)workspace, dw,
-                     d->Cout, d->Cin, T, pl.co_p, pl.ci_p, pl.splits, PB, scaled ? x_bound : (const float*)nullptr,
-                     scaled ? dy_bound : (const float*)nullptr);
-  MCD_LAUNCH_CHECK("conv_wgrad_reduce");
-  return 0;
 }

@@ -639,3 +639,49 @@ def test_conv_launch_table_of_every_layer(golden):
                 want = table.lookup(t, gi, si)
                 for key in t["keys"]:
                     assert got[key] == want[key], (g, setting, key)
+
+
+def test_conv_plan_answers_of_every_layer(golden):
+    """tests/golden/conv_plan_answers.json (make_conv_plan_answers.py: taken before each convolution pass got one route in the library) --
+    every plan query of include/mcdseg.h, for the geometries of the launch table at N, at 2 N and as a half-batch slice, under every
+    ``math``, ``presplit`` and ``dgrad``, the default options and each plan option alone: every answer is recomputed and must equal the
+    recorded one.  Host arithmetic only."""
+    import make_conv_plan_answers as answers
+    import make_conv_launch_table as table
+    import mcdseg
+    from mcdseg import ops
+    t = golden.json("conv_plan_answers.json")
+    assert t["settings"] == answers.settings() and t["keys"] == list(answers.KEYS) and t["maths"] == list(answers.MATHS)
+    assert t["fields"] == list(table.FIELDS) and t["forms"] == list(answers.FORMS) and len(t["geometries"]) >= 80
+    assert len(t["table"]) == len(t["geometries"]) * len(t["forms"]) and all(len(row) == len(t["settings"]) for row in t["table"])
+    L = ops.lib()
+    descs = [d for g in t["geometries"] for d in answers.forms(ops, g)]
+    for si, setting in enumerate(t["settings"]):
+        with mcdseg.options(**setting):
+            for row, d in enumerate(descs):
+                got, want = json.loads(json.dumps(answers.record(L, d))), answers.lookup(t, row, si)
+                for key in t["keys"]:
+                    assert got[key] == want[key], (t["geometries"][row // 3], t["forms"][row % 3], setting, key)
+
+
+def test_stem_forward_refuses_partial_rows_it_was_not_asked_for():
+    """include/mcdseg.h: ``mcdseg_conv_split_stat_rows_for`` answers for a call without bias / affine epilogue.  The stem with a companion
+    AND a bias runs on the direct kernel, whose partial rows are not the window kernel's that the query counts: such a call with
+    ``stat_partials`` is refused before anything is launched; without the bias, or without the companion, it is not.  No GPU: the
+    pointers are never dereferenced (``part`` 1 of a stem launches nothing)."""
+    import ctypes
+    from mcdseg import ops
+    L = ops.lib()
+    d = ops.conv_desc((16, 6, 480, 640), (16, 6, 7, 7), 1, 3, 1)
+    r, fake = ctypes.byref(d), [ctypes.c_void_p(0x1000 * (i + 1)) for i in range(8)]
+    x, x_cb, x_bound, wp, w_bound, bias, y, stats = fake
+    assert L.mcdseg_conv_split_direct_ok(r) == 1 and L.mcdseg_conv_split_window_ok(r, 3, 1, 0) == 1
+    asked, direct = L.mcdseg_conv_split_stat_rows_for(r, 3, 1), L.mcdseg_conv_split_stat_rows(r)
+    assert (asked, direct) == (2048, 38400) and L.mcdseg_conv_split_stat_rows_for(r, 3, 0) == direct
+    for part in (0, 1):
+        assert L.mcdseg_conv_split_fprop_part(r, 3, x, x_cb, x_bound, wp, w_bound, bias, y, stats, part, None) == -22
+        msg = L.mcdseg_last_error().decode()
+        assert "bias / affine epilogue" in msg and "38400 partial-statistics rows, not the 2048" in msg and "stat_rows_for" in msg, msg
+    assert L.mcdseg_conv_split_fprop_part(r, 3, x, x_cb, x_bound, wp, w_bound, None, y, stats, 1, None) == 0   # no bias: the window kernel
+    assert L.mcdseg_conv_split_fprop_part(r, 3, x, None, x_bound, wp, w_bound, bias, y, stats, 1, None) == 0   # no companion: the direct kernel
+    assert L.mcdseg_conv_split_fprop_part(r, 3, x, x_cb, x_bound, wp, w_bound, bias, y, None, 1, None) == 0    # no statistics asked for
