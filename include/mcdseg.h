@@ -261,6 +261,44 @@ int mcdseg_unsplit_cb(const void* x_cb, const float* x_bound, int32_t math, int3
  * apply (C % 8, N * C/8 > 65535); every refusal is answered before anything is launched. */
 int mcdseg_stage_join(const float* a, const float* a_bound, const float* b, const float* b_bound, float* y, void* y_cb, float* y_bound,
                       int32_t math, int32_t N, int32_t C, int32_t HW, void* stream);
+/* The operators of the U-Net generator and classifiers (models/unet.py of the reference: UNetBase :122-171, UNetUp :29-43,
+ * UNetClassifier :174-199), fp32 NCHW.  No float atomics: every result is the same bits run to run.  Every refusal is -EINVAL with a
+ * mcdseg_last_error message, answered before anything is launched.
+ *
+ * mcdseg_maxpool2_fwd / _bwd: nn.MaxPool2d(kernel_size=2) (:135-159).  H and W must be even.  y[n,c,i,j] is the maximum of the 2x2
+ * window by torch's CPU rule: the window is walked (0,0), (0,1), (1,0), (1,1) from -inf and a value takes over when it is greater than
+ * the best so far or is a NaN -- the first of equal values wins (-0 against +0 included), a NaN wins over what came before it.  The
+ * backward takes x and dy and writes EVERY element of dx: dy at the window's arg-max (recomputed from x: no index tensor exists), 0 at
+ * the other three.  y_cb != NULL: the companion of y in the same pass, [piece][N][C/8][Ho*Wo][8 x 16 bit], bitwise what
+ * mcdseg_split_cb(y, y_bound) writes, with y_bound[0] = x_bound[0] (|max| cannot exceed the bound of x: nothing is reduced); then the
+ * refusals of mcdseg_split_cb apply (C % 8, N * C/8 > 65535, MCDSEG_MATH_F16X3 / _F16X1 without the bounds).  The bounds come as both
+ * pointers or none.
+ *
+ * mcdseg_relu_fwd / _bwd: the nn.ReLU behind the BatchNorm-less convolutions of UNetUp (:18-21).  y = x < 0 ? +0 : x (torch's
+ * clamp: -0 and NaN pass); y may be x.  The companion and the bound as for the pool.  Backward: dx = y > 0 ? dy : 0, from y; dx may be dy.
+ *
+ * mcdseg_deconv2x2_fwd / _bwd_data / _bwd_weight: nn.ConvTranspose2d(Cin, Cout, kernel_size=2, stride=2) (:34),
+ *   y[n,co,2i+a,2j+b] = bias[co] + sum_ci x[n,ci,i,j] * w[ci,co,a,b]
+ * with w in torch's [Cin][Cout][2][2] layout as the parameter holds it (bias may be NULL) and x [N][Cin][H][W].  y and dy are channel
+ * slices of a larger buffer (the concatenation torch.cat([shortcut, up(h)], 1) of :43): element (n, co, r, s) lies at
+ * base[n * batch_stride + (channel_offset + co) * 4*H*W + r * 2*W + s], `channels` being the buffer's channel count; a slice outside
+ * the buffer (channel_offset + Cout > channels, batch_stride < channels * 4*H*W) is refused.  Plain fp32 FMA chains in a fixed order.
+ * _bwd_weight writes dw [Cin][Cout][2][2] and db [Cout] (db may be NULL) in two stages: fp64 block partials in the workspace
+ * (mcdseg_deconv2x2_bwd_weight_workspace_bytes, 8-byte aligned), then one finalize kernel. */
+int mcdseg_maxpool2_fwd(const float* x, const float* x_bound, float* y, void* y_cb, float* y_bound, int32_t math, int32_t N, int32_t C,
+                        int32_t H, int32_t W, void* stream);
+int mcdseg_maxpool2_bwd(const float* x, const float* dy, float* dx, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
+int mcdseg_relu_fwd(const float* x, const float* x_bound, float* y, void* y_cb, float* y_bound, int32_t math, int32_t N, int32_t C,
+                    int32_t HW, void* stream);
+int mcdseg_relu_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream);
+int mcdseg_deconv2x2_fwd(const float* x, const float* w, const float* bias, float* y, int64_t y_batch_stride, int32_t y_channels,
+                         int32_t y_channel_offset, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W, void* stream);
+int mcdseg_deconv2x2_bwd_data(const float* dy, int64_t dy_batch_stride, int32_t dy_channels, int32_t dy_channel_offset, const float* w,
+                              float* dx, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W, void* stream);
+size_t mcdseg_deconv2x2_bwd_weight_workspace_bytes(int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W);
+int mcdseg_deconv2x2_bwd_weight(const float* x, const float* dy, int64_t dy_batch_stride, int32_t dy_channels, int32_t dy_channel_offset,
+                                float* dw, float* db, int32_t N, int32_t Cin, int32_t Cout, int32_t H, int32_t W, void* workspace,
+                                size_t workspace_bytes, void* stream);
 int mcdseg_bn_apply_cb(const float* z, const float* mean, const float* rstd, const float* gamma, const float* beta,
                        const float* residual, const void* res_cb, const float* res_bound, float* y, void* y_cb,
                        const float* y_bound, int32_t math, int32_t N, int32_t C, int32_t HW, int32_t relu, void* stream);

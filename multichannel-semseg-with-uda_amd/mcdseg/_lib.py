@@ -81,6 +81,16 @@ _SIGNATURES = {
     "mcdseg_split_cb_padded": (c_int, [c_void_p, c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p]),
     "mcdseg_unsplit_cb": (c_int, [c_void_p, c_void_p, c_i32, c_i32, c_i32, c_i32, c_void_p, c_void_p]),
     "mcdseg_stage_join": (c_int, [c_void_p] * 7 + [c_i32] * 4 + [c_void_p]),
+    # the U-Net operators (csrc/unet.hip)
+    "mcdseg_maxpool2_fwd": (c_int, [c_void_p] * 5 + [c_i32] * 5 + [c_void_p]),
+    "mcdseg_maxpool2_bwd": (c_int, [c_void_p] * 3 + [c_i32] * 4 + [c_void_p]),
+    "mcdseg_relu_fwd": (c_int, [c_void_p] * 5 + [c_i32] * 4 + [c_void_p]),
+    "mcdseg_relu_bwd": (c_int, [c_void_p] * 3 + [c_i64, c_void_p]),
+    "mcdseg_deconv2x2_fwd": (c_int, [c_void_p] * 4 + [c_i64] + [c_i32] * 7 + [c_void_p]),
+    "mcdseg_deconv2x2_bwd_data": (c_int, [c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p] + [c_i32] * 5 + [c_void_p]),
+    "mcdseg_deconv2x2_bwd_weight_workspace_bytes": (c_size_t, [c_i32] * 5),
+    "mcdseg_deconv2x2_bwd_weight": (c_int, [c_void_p, c_void_p, c_i64, c_i32, c_i32, c_void_p, c_void_p] + [c_i32] * 5 +
+                                    [c_void_p, c_size_t, c_void_p]),
     "mcdseg_bn_apply_cb": (c_int, [c_void_p] * 11 + [c_i32] * 5 + [c_void_p]),
     "mcdseg_bn_bwd_apply_cb": (c_int, [c_void_p] * 13 + [c_i32] * 6 + [c_void_p]),
     "mcdseg_bn_bwd_reduce_zmask": (c_int, [c_void_p] * 9 + [c_i32] * 4 + [c_void_p, c_size_t, c_void_p]),
@@ -191,7 +201,7 @@ def sources():
 # backward under two ranks per device.  The compiler forms these instructions on its own from scalar fp32 source code, so the
 # files below are compiled with the packed-fp32 feature off, and ``packed_f32_opsel_sites`` (tests/test_cabi_and_host.py)
 # disassembles the built library to prove that no such instruction is left in ANY kernel.
-NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip", "seg2bd.hip", "augment.hip", "uncertain.hip", "dann.hip", "join.hip"}
+NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip", "seg2bd.hip", "augment.hip", "uncertain.hip", "dann.hip", "join.hip", "unet.hip"}
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden"]
 NO_PK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # (the host pass ignores it with a warning)
 OBJ_DIR = os.path.join(CSRC, "build")

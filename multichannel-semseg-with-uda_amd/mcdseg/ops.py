@@ -6,6 +6,9 @@ mirror the ATen call sites of the reference's hot path:
 
   conv_bn_act      nn.Conv2d + nn.BatchNorm2d + ReLU (+ residual)   models/drn.py:43-59, 80-100, 195-205
   stage_join       torch.add between two stage outputs (+ the next stage's operand)   models/dilated_fcn.py:308-328
+  max_pool2        nn.MaxPool2d(kernel_size=2) (+ the next convolution's operand)     models/unet.py:135-159
+  up_join          torch.cat([shortcut, ConvTranspose2d k2 s2 (h)], 1)                models/unet.py:38-43
+  relu             nn.ReLU behind a convolution without BatchNorm                     models/unet.py:18-21
   conv2d_bias      nn.Conv2d with bias (the 1x1 ``seg`` head)       models/dilated_fcn.py:226-232
   up8 / up8_dual   depthwise ConvTranspose2d k16 s8 p4              models/dilated_fcn.py:357-366, 479-491
   cross_entropy2d  log_softmax + weighted NLL                       loss.py:7-13
@@ -1546,6 +1549,7 @@ def conv_bn_act(x, conv, bn, relu=True, residual=None, internal=False, in_box=No
         raise NotImplementedError("mcdseg: eval-mode BatchNorm needs running statistics")
     momentum = 0.1 if bn.momentum is None else bn.momentum
     x_cb, x_bound = _cb_of(x)
+    x_cb = _cb_unless_biased_window(x, conv, geom, x_cb)
     if x_cb is not None and conv.in_channels <= 16 and x_cb.numel() == x.numel() and PIECES.get(CONV_MATH, 0) > 1:
         # (the thin layers' window kernels multiply BOTH pieces of their operand whatever the arithmetic; no network of the reference
         # feeds a 16-channel convolution from inside the 2-byte chain, whose groups all have more than 16 input channels)
@@ -1570,6 +1574,33 @@ def conv_bn_act(x, conv, bn, relu=True, residual=None, internal=False, in_box=No
     if y.stride(0) == 0 and y.numel() > 1:
         y._mcd_virtual = True  # compact storage: the companion IS the activation
     return y
+
+
+def _cb_unless_biased_window(x, conv, geom, x_cb):
+    """``x_cb``, or None where handing it on would be refused: given a companion, the library routes a thin 3x3 convolution to the
+    LDS-window kernel (csrc/conv_thin_window.hip), which has no bias epilogue.  A convolution WITH a bias at such a geometry (the
+    16-channel layers of the U-Net: no DRN has one) reads the fp32 tensor instead and splits it in its K loop -- the same values."""
+    if x_cb is None or conv.bias is None or is_virtual(x):
+        return x_cb
+    return None if _biased_window(conv, x.shape, geom) else x_cb
+
+
+def _biased_window(conv, x_shape, geom):
+    """a convolution with a bias at a geometry that the library, given a companion, routes to the LDS-window kernel"""
+    if conv.bias is None or CONV_MATH not in MATH_ID:
+        return False
+    d = conv_desc(x_shape, conv.weight.shape, *geom)
+    return bool(_memo(d, ("biased_window",), lambda: lib().mcdseg_conv_split_window_ok(ctypes.byref(d), MATH_ID[CONV_MATH], 1, 0)))
+
+
+def conv_reads_companion(conv, x_shape):
+    """Will ``conv`` (a parameter holder of models/drn.py), run through ``conv_bn_act`` or ``conv2d_bias`` on an input of this shape, read
+    the pre-split companion its producer attaches?  What a producer that knows its one consumer asks before it writes one
+    (``max_pool2`` / ``relu`` / ``up_join`` take the answer as ``companion=``): no for the biased thin layers above, and where the layout
+    does not apply."""
+    n, c = int(x_shape[0]), int(x_shape[1])
+    geom = (conv.stride[0], conv.padding[0], conv.dilation[0])
+    return bool(_cb_wanted(c) and _cb_grid_ok(n, c) and not _biased_window(conv, x_shape, geom))
 
 
 def _cb_of(x):
@@ -1650,6 +1681,200 @@ def stage_join(a, b):
     return y
 
 
+# ------------------------------------------------------------------------------------------------ U-Net: pool, up-convolution + join, ReLU
+def fused_unet():
+    """MCDSEG_FUSED_UNET=0 (host-side, read at every call): ``max_pool2``, ``up_join`` and ``relu`` compose their results from
+    ``F.max_pool2d``, ``F.conv_transpose2d`` + ``torch.cat``, ``torch.relu`` and ``split_companion`` instead of the kernels of
+    csrc/unet.hip -- the pool and the ReLU bitwise the same, the up-convolution another summation order; the parity test's other side and
+    the timing baseline"""
+    return os.environ.get("MCDSEG_FUSED_UNET", "1") != "0"
+
+
+def _unary_plan(x, what, companion=True):
+    """what ``max_pool2`` and ``relu`` decide alike, by ``stage_join``'s rules: (x, plain, want_cb, x_bound).  ``companion=False``: the
+    caller knows that nothing will read a companion of the result (``conv_reads_companion``) -- none is written, and a bound is handed on
+    only where ``x`` carries one already (nothing is measured for a reader that may not exist)"""
+    if is_virtual(x):
+        raise RuntimeError("mcdseg: %s takes an fp32 activation, not one kept as its companion" % what)
+    if x.dim() != 4:
+        raise ValueError("mcdseg: %s takes an NCHW tensor, got %s" % (what, tuple(x.shape)))
+    x = _req(x, what + " input")
+    n, c = x.shape[0], x.shape[1]
+    cb, bound = _cb_of(x)
+    plain = not torch.is_grad_enabled() and cb is None and bound is None
+    want_cb = bool(companion and not plain and _cb_wanted(c) and _cb_grid_ok(n, c))
+    x_bound = None
+    if _scaled() and not plain and (want_cb or _use_split(c)):
+        x_bound = _bound_or_measure(x, bound) if companion else bound
+    return x, plain, want_cb, x_bound
+
+
+def _attach(y, y_cb, y_bound):
+    if y_cb is not None or y_bound is not None:
+        y._mcd_cb = (y_cb, y_bound, y._version, y.data_ptr())
+    return y
+
+
+class _MaxPool2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, x_bound, want_cb):
+        n, c, h, w = x.shape
+        y = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+        y_cb = _cb_alloc(n, c, (h // 2) * (w // 2), x.device) if want_cb else None
+        y_bound = torch.empty(1, dtype=torch.float32, device=x.device) if x_bound is not None else None
+        cb_bytes = 2 * PIECES[CONV_MATH] if want_cb else 0
+        with _timed("maxpool2_fwd", (0, n * c * (h // 2) * (w // 2) * (20 + cb_bytes))):
+            check(lib().mcdseg_maxpool2_fwd(_p(x), _p(x_bound), _p(y), _p(y_cb), _p(y_bound), MATH_ID.get(CONV_MATH, 0), n, c, h, w,
+                                            _stream()), "maxpool2_fwd")
+        ctx.save_for_backward(x)
+        ctx.set_materialize_grads(False)
+        for t in (y_cb, y_bound):
+            if t is not None:
+                ctx.mark_non_differentiable(t)
+        return y, y_cb, y_bound
+
+    @staticmethod
+    def backward(ctx, dy, _dcb=None, _dbound=None):
+        if dy is None:
+            return None, None, None
+        (x,) = ctx.saved_tensors
+        n, c, h, w = x.shape
+        dy = _req(dy, "grad_output")
+        dx = torch.empty_like(x)
+        with _timed("maxpool2_bwd", (0, n * c * h * w * 9)):
+            check(lib().mcdseg_maxpool2_bwd(_p(x), _p(dy), _p(dx), n, c, h, w, _stream()), "maxpool2_bwd")
+        return dx, None, None
+
+
+def max_pool2(x, companion=True):
+    """``nn.MaxPool2d(kernel_size=2)`` (models/unet.py:135-159) with what the next convolution reads attached to the result the way
+    ``stage_join`` attaches it: the pre-split companion -- when ``_cb_wanted(C)`` and the grid fits -- and the bound of ``x`` (|max|
+    cannot exceed it).  Ties and NaN by torch's CPU rule; the backward recomputes the arg-max from ``x``.  Without grad mode and with an
+    input that carries neither a companion nor a bound only ``y`` is written.  ``companion=False``: see ``_unary_plan``."""
+    if x.dim() == 4 and (x.shape[2] % 2 or x.shape[3] % 2):  # (refused before anything -- a bound's measurement included -- is launched)
+        raise ValueError("mcdseg: max_pool2 takes even H and W, got %d x %d" % (x.shape[2], x.shape[3]))
+    x, plain, want_cb, x_bound = _unary_plan(x, "max_pool2", companion)
+    if not fused_unet():
+        y = torch.nn.functional.max_pool2d(x, 2)
+        return _attach(y, split_companion(y, x_bound)[0] if want_cb else None, x_bound)
+    return _attach(*_MaxPool2.apply(x, x_bound, want_cb))
+
+
+class _ReLU(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, x_bound, want_cb):
+        n, c, h, w = x.shape
+        y = torch.empty_like(x)
+        y_cb = _cb_alloc(n, c, h * w, x.device) if want_cb else None
+        y_bound = torch.empty(1, dtype=torch.float32, device=x.device) if x_bound is not None else None
+        cb_bytes = 2 * PIECES[CONV_MATH] if want_cb else 0
+        with _timed("relu_fwd", (0, n * c * h * w * (8 + cb_bytes))):
+            check(lib().mcdseg_relu_fwd(_p(x), _p(x_bound), _p(y), _p(y_cb), _p(y_bound), MATH_ID.get(CONV_MATH, 0), n, c, h * w, _stream()),
+                  "relu_fwd")
+        ctx.save_for_backward(y)
+        ctx.set_materialize_grads(False)
+        for t in (y_cb, y_bound):
+            if t is not None:
+                ctx.mark_non_differentiable(t)
+        return y, y_cb, y_bound
+
+    @staticmethod
+    def backward(ctx, dy, _dcb=None, _dbound=None):
+        if dy is None:
+            return None, None, None
+        (y,) = ctx.saved_tensors
+        dy = _req(dy, "grad_output")
+        dx = torch.empty_like(y)
+        with _timed("relu_bwd", (0, y.numel() * 12)):
+            check(lib().mcdseg_relu_bwd(_p(y), _p(dy), _p(dx), y.numel(), _stream()), "relu_bwd")
+        return dx, None, None
+
+
+def relu(x, companion=True):
+    """the ``nn.ReLU`` behind a convolution without BatchNorm (``UNetConv(..., is_batchnorm=False)``, models/unet.py:18-21): a negative
+    value becomes +0, anything else passes (torch's clamp), with the companion and the bound of ``x`` attached as ``max_pool2`` does
+    (``companion=False``: as there).  Backward: dx = y > 0 ? dy : 0."""
+    x, plain, want_cb, x_bound = _unary_plan(x, "relu", companion)
+    if not fused_unet():
+        y = torch.relu(x)
+        return _attach(y, split_companion(y, x_bound)[0] if want_cb else None, x_bound)
+    return _attach(*_ReLU.apply(x, x_bound, want_cb))
+
+
+class _UpJoin(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, shortcut, h, weight, bias):
+        L = lib()
+        n, cin, hh, wh = h.shape
+        cs, cout = shortcut.shape[1], weight.shape[1]
+        ct, hw4 = cs + cout, 4 * hh * wh
+        y = torch.empty((n, ct, 2 * hh, 2 * wh), dtype=torch.float32, device=h.device)
+        if cs:
+            y[:, :cs].copy_(shortcut)  # the copy torch.cat makes
+        with _timed("deconv2x2_fwd", (2 * n * hw4 * cin * cout, 4 * n * hh * wh * (cin + 4 * cout))):
+            check(L.mcdseg_deconv2x2_fwd(_p(h), _p(weight), _p(bias), _p(y), ct * hw4, ct, cs, n, cin, cout, hh, wh, _stream()), "deconv2x2_fwd")
+        ctx.save_for_backward(h, weight)
+        ctx.cs, ctx.has_bias = cs, bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        L = lib()
+        h, weight = ctx.saved_tensors
+        n, cin, hh, wh = h.shape
+        cs, cout = ctx.cs, weight.shape[1]
+        ct, hw4 = cs + cout, 4 * hh * wh
+        dy = _req(dy, "grad_output")
+        need_s, need_h, need_w, need_b = ctx.needs_input_grad
+        ds = dy[:, :cs] if (need_s and cs) else None  # the lower slice of the incoming gradient, as torch.cat's backward hands it on
+        dh = dw = db = None
+        if need_h:
+            dh = torch.empty_like(h)
+            with _timed("deconv2x2_bwd_data", (2 * n * hw4 * cin * cout, 4 * n * hh * wh * (cin + 4 * cout))):
+                check(L.mcdseg_deconv2x2_bwd_data(_p(dy), ct * hw4, ct, cs, _p(weight), _p(dh), n, cin, cout, hh, wh, _stream()),
+                      "deconv2x2_bwd_data")
+        if need_w or (need_b and ctx.has_bias):
+            dw = torch.empty_like(weight)
+            db = torch.empty(cout, dtype=torch.float32, device=h.device) if ctx.has_bias else None
+            ws = _ws64(L.mcdseg_deconv2x2_bwd_weight_workspace_bytes(n, cin, cout, hh, wh), h.device)
+            with _timed("deconv2x2_bwd_weight", (2 * n * hw4 * cin * cout, 4 * n * hh * wh * (cin + 4 * cout))):
+                check(L.mcdseg_deconv2x2_bwd_weight(_p(h), _p(dy), ct * hw4, ct, cs, _p(dw), _p(db), n, cin, cout, hh, wh, _p(ws),
+                                                    ctypes.c_size_t(ws.numel() * 8), _stream()), "deconv2x2_bwd_weight")
+        return ds, dh, dw if need_w else None, db if (need_b and ctx.has_bias) else None
+
+
+def up_join(shortcut, h, up_weight, up_bias, companion=True):
+    """``torch.cat([shortcut, up(h)], 1)`` with ``up = nn.ConvTranspose2d(Cin, Cout, kernel_size=2, stride=2)`` (``UNetUp.forward``,
+    models/unet.py:38-43, at offset 0): one [N, Cs + Cout, 2H, 2W] buffer, ``shortcut`` copied into channels [0, Cs) and the up-convolution
+    written straight into [Cs, Cs + Cout).  ``up_weight`` is torch's [Cin, Cout, 2, 2] parameter, read as it is.  The backward hands
+    ``shortcut`` the lower slice of the incoming gradient and forms dh, dw, db from the upper slice in place.  The result carries a
+    companion and a bound by ``stage_join``'s rules -- the bound measured: an up-convolution has no bound known in advance.
+    ``companion=False`` (the caller knows that no reader of a companion follows, ``conv_reads_companion``): neither is formed."""
+    for t, name in ((shortcut, "shortcut"), (h, "h")):
+        if is_virtual(t):
+            raise RuntimeError("mcdseg: up_join takes fp32 activations, not ones kept as their companions (%s)" % name)
+    if shortcut.dim() != 4 or h.dim() != 4 or up_weight.dim() != 4 or tuple(up_weight.shape[2:]) != (2, 2) or up_weight.shape[0] != h.shape[1]:
+        raise ValueError("mcdseg: up_join takes NCHW tensors and a [Cin, Cout, 2, 2] weight, got %s, %s and %s"
+                         % (tuple(shortcut.shape), tuple(h.shape), tuple(up_weight.shape)))
+    if shortcut.shape[0] != h.shape[0] or shortcut.shape[2] != 2 * h.shape[2] or shortcut.shape[3] != 2 * h.shape[3]:
+        raise ValueError("mcdseg: up_join takes a shortcut of twice the size of h (the reference pads or crops: not built), got %s and %s"
+                         % (tuple(shortcut.shape), tuple(h.shape)))
+    shortcut, h = _req(shortcut, "up_join shortcut"), _req(h, "up_join input")
+    up_weight, up_bias = _req(up_weight, "up_join weight"), _req(up_bias, "up_join bias")
+    recs = (_cb_of(shortcut), _cb_of(h))
+    plain = not torch.is_grad_enabled() and all(cb is None and bound is None for cb, bound in recs)
+    if fused_unet():
+        y = _UpJoin.apply(shortcut, h, up_weight, up_bias)
+    else:
+        y = torch.cat([shortcut, torch.nn.functional.conv_transpose2d(h, up_weight, up_bias, stride=2)], 1)
+    n, c = y.shape[0], y.shape[1]
+    if plain or not companion:
+        return y
+    if _cb_wanted(c) and _cb_grid_ok(n, c):
+        return _attach(y, *split_companion(y))
+    return _attach(y, None, _bound_or_measure(y, None) if _use_split(c) else None)
+
+
 # ------------------------------------------------------------------------------------------------ conv (+bias)
 class _Conv2dBias(torch.autograd.Function):
     @staticmethod
@@ -1685,6 +1910,7 @@ def conv2d_bias(x, conv):
     if is_virtual(x):
         raise RuntimeError("mcdseg: a compact activation left its trunk (the trunk's last layer writes fp32)")
     x_cb, x_bound = _cb_of(x)
+    x_cb = _cb_unless_biased_window(x, conv, geom, x_cb)
     if _FWD_SYNC == "follow" and _FWD_LEAD_DONE is not None:
         # a convolution without BatchNorm has no per-layer event: the follower of a ForwardFork runs it behind the whole leading pass
         torch.cuda.current_stream().wait_event(_FWD_LEAD_DONE)

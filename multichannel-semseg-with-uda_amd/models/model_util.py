@@ -1,7 +1,7 @@
 """Model / optimizer factory with the reference's names and signatures (models/model_util.py:6-39, 160-310).
 
-Only the DRN branches -- the ones the MCD hot path uses -- are implemented; every other network name
-raises ``NotImplementedError`` (the reference's message is kept).  ``get_optimizer('sgd')`` returns the
+The DRN branches -- the ones the MCD hot path uses -- and ``get_models("unet", ..., method="MCD")`` (models/unet.py) are
+implemented; every other network name raises ``NotImplementedError`` (the reference's message is kept).  ``get_optimizer('sgd')`` returns the
 flat-buffer HIP SGD (``mcdseg.optim.FlatSGD``) and ``get_optimizer('adam')`` the flat-buffer HIP Adam
 (``mcdseg.optim.FlatAdam``, betas (0.5, 0.999) as in the reference), state-dict compatible with ``torch.optim.SGD`` /
 ``torch.optim.Adam``; both sum their gradients over the ranks of a data-parallel run.  ``'adadelta'``, which the
@@ -54,6 +54,13 @@ def get_full_uncertain_model(net, res, n_class, input_ch, criterion, is_data_par
 
 
 def get_models(net_name, input_ch, n_class, res="50", method="MCD", is_data_parallel=False):
+    if net_name == "unet":
+        # models/model_util.py:205-210 of the reference: the U-Net generator and two of its classifiers at the default feature_scale
+        if method != "MCD":
+            raise NotImplementedError("the U-Net (%s) is built for method \"MCD\" only (the MFNet U-Net, MultiUNetClassifier, is not), "
+                                      "got %r" % (net_name, method))
+        from models.unet import UNetBase, UNetClassifier
+        return _wrap([UNetBase(input_ch=input_ch), UNetClassifier(n_classes=n_class), UNetClassifier(n_classes=n_class)], is_data_parallel)
     if "drn" not in net_name:
         raise NotImplementedError("Only FCN (Including Dilated FCN), SegNet, PSPNet UNet are supported!")
     from models.dilated_fcn import (DRNSegBase, DRNSegPixelClassifier, FuseDRNSegBase, FusionDRNSegPixelClassifier,

@@ -55,9 +55,11 @@ def _second_stream(device, cur):
 
 def _detached(t):
     """``t.detach()`` that keeps the pre-split companion the producer attached (same storage, same version counter); maps over
-    tuples / lists of tensors"""
+    tuples / lists / dicts of tensors (``UNetBase`` returns a dict of feature maps)"""
     if isinstance(t, (tuple, list)):
         return type(t)(_detached(v) for v in t)
+    if isinstance(t, dict):
+        return {k: _detached(v) for k, v in t.items()}
     d = t.detach()
     for a in ("_mcd_cb", "_mcd_virtual"):
         if hasattr(t, a):
