@@ -695,6 +695,28 @@ int mcdseg_boundary_regions(const uint8_t* boundary, int32_t thre, int32_t* regi
 int mcdseg_refine_labels_by_regions(const uint8_t* seg, const int32_t* regions, uint8_t* out, int32_t N, int32_t H, int32_t W,
                                     int32_t min_thre, int32_t max_thre, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The fully connected CRF over saved logits (tools/crf.py:14-60 dense_crf, :63-66 softmax, :95-112 the driver) with the pairwise sums
+ * taken exactly, not on pydensecrf's lattice (csrc/crf.hip).  Per image, N = H*W:
+ *   U = -log_softmax(z) over C (finite where tools/crf.py:48 -log(softmax) gives inf); Q^0 = softmax(-U);
+ *   Q^{t+1} = softmax(-U + w_g M_g(Q^t) + w_b M_b(Q^t)), M_i = n_i sum_j k(i,j) n_j Q_j, n_i = 1 / sqrt(sum_j k(i,j) + 1e-20),
+ *   k(i,j) = exp(-0.5 |f_i - f_j|^2) with j = i included; f = (x/sx, y/sy) for the Gaussian term (crf.py:51-52) and
+ *   (x/sx, y/sy, r/sr, g/sg, b/sb) for the bilateral one (crf.py:55-57), which exists only with an image.
+ *   logits  fp32 [B,C,H,W] (what prob/<name>.npy holds, crf.py:95);  rgb uint8 [B,H,W,3] or NULL: no bilateral term (crf.py:53, :110);
+ *   params  10 floats ON THE HOST in the order of crf.py:14-21: sxy_gaussian x, y; compat_gaussian; sxy_bilateral x, y;
+ *           compat_bilateral; srgb_bilateral r, g, b; the tenth is reserved and not read.  n_iters (crf.py:14, :58) is an argument;
+ *   q       fp32 [B,C,H,W] = Q^{n_iters}, may be NULL;  labels uint8 [B,H,W] = the arg-max over the first C_used classes (crf.py:112 takes
+ *           19), the first maximum on a tie, may be NULL (not both).  n_iters = 0 returns softmax(z).
+ * The Gaussian term is summed over |dx| <= ceil(7.5 sx), |dy| <= ceil(7.5 sy): a pair outside has k < exp(-28.125) < 2^-40, and what one
+ * pixel loses altogether is below 1e-12 sx sy against a sum >= 1.  The bilateral term is summed over ALL pairs of an image.  Images of a
+ * batch never pair.  fp32 throughout, no float atomics: the same bits run to run and for an image alone or in a batch.
+ * -EINVAL before anything is launched: C outside [1, 64]; C_used outside [1, C]; n_iters < 0; a standard deviation that is not positive
+ * and finite (the bilateral ones only with an image); H*W > 2^24, B*H*W*64 >= 2^31 or B > 65535 (what the index arithmetic covers);
+ * a workspace smaller than mcdseg_dense_crf_workspace_bytes (4 x [B N][C up to 32 or 64] floats + n_g; with an image n_b and 8 feature
+ * floats per pixel; each part padded to 256 bytes; 0 for dims that are refused) or not 16-byte aligned. */
+size_t mcdseg_dense_crf_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t W, int32_t with_image);
+int mcdseg_dense_crf(const float* logits, const uint8_t* rgb, const float* params, float* q, uint8_t* labels, int32_t C_used, int32_t B,
+                     int32_t C, int32_t H, int32_t W, int32_t n_iters, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2-byte activation storage (round 6): BASELINE config 5 ("drn_d_105 ... bf16 ... HBM-bound stress"; the network is the reference's
  * Bottleneck trunk, models/drn.py:62-100, 344-348, trained by adapt_trainer.py:155-220).  In the one-term arithmetic MCDSEG_MATH_F16X1

@@ -2938,6 +2938,108 @@ def refine_labels_by_boundary(seg_u8, boundary_u8, thre=50, min_thre=500, max_th
     return refine_labels(seg_u8, boundary_regions(boundary_u8, thre), min_thre, max_thre)
 
 
+# ------------------------------------------------------------------------------------------------ dense CRF over saved logits
+CRF_DEFAULTS = {"n_iters": 10, "sxy_gaussian": (1, 1), "compat_gaussian": 4, "sxy_bilateral": (49, 49), "compat_bilateral": 5,
+                "srgb_bilateral": (13, 13, 13)}  # tools/crf.py:14-21
+
+
+def fused_crf():
+    """MCDSEG_FUSED_CRF=0 (host-side, read at every call): ``dense_crf`` composes the same definition from torch -- row chunks of
+    ``torch.exp(-0.5 * cdist ** 2) @ (n * Q)`` for both terms -- instead of the kernels of csrc/crf.hip: the parity test's other side
+    and the timing baseline"""
+    return os.environ.get("MCDSEG_FUSED_CRF", "1") != "0"
+
+
+def _pair(v, k, name):
+    v = tuple(float(a) for a in (v if isinstance(v, (tuple, list)) else (v,) * k))
+    if len(v) != k:
+        raise ValueError("mcdseg: dense_crf %s takes %d values, got %d" % (name, k, len(v)))
+    return v
+
+
+def _crf_composed(z, rgb, n_iters, params, c_used):
+    """the definition of DESIGN.md section 4.12 in torch, fp32, every sum over all pixels of the image (the Gaussian term included)"""
+    b, c, h, w = z.shape
+    sxg, syg, wg, sxb, syb, wb, sr, sg, sb = params
+    n = h * w
+    ys, xs = torch.meshgrid(torch.arange(h, device=z.device, dtype=torch.float32), torch.arange(w, device=z.device, dtype=torch.float32),
+                            indexing="ij")
+    xs, ys = xs.reshape(n), ys.reshape(n)
+    chunk = max(1, min(n, (1 << 27) // n))
+
+    def kernel_rows(f, lo, hi):
+        return torch.exp(-0.5 * torch.cdist(f[lo:hi], f, compute_mode="donot_use_mm_for_euclid_dist") ** 2)
+
+    def norm(f):
+        s = torch.cat([kernel_rows(f, lo, min(lo + chunk, n)).sum(1) for lo in range(0, n, chunk)])
+        return 1.0 / torch.sqrt(s + 1e-20)
+
+    def message(f, nrm, q):  # q [n, c]
+        nq = nrm[:, None] * q
+        return nrm[:, None] * torch.cat([kernel_rows(f, lo, min(lo + chunk, n)) @ nq for lo in range(0, n, chunk)])
+
+    q_out = torch.empty((b, c, h, w), dtype=torch.float32, device=z.device)
+    for k in range(b):
+        u = -torch.log_softmax(z[k].reshape(c, n).t(), dim=1)
+        terms = [(torch.stack([xs / sxg, ys / syg], 1), wg)]
+        if rgb is not None:
+            px = rgb[k].reshape(n, 3).float()
+            terms.append((torch.stack([xs / sxb, ys / syb, px[:, 0] / sr, px[:, 1] / sg, px[:, 2] / sb], 1), wb))
+        q = torch.softmax(-u, dim=1)
+        if n_iters > 0:
+            norms = [norm(f) for f, _ in terms]
+        for _ in range(n_iters):
+            x = -u
+            for (f, wt), nrm in zip(terms, norms):
+                x = x + wt * message(f, nrm, q)
+            q = torch.softmax(x, dim=1)
+        q_out[k] = q.t().reshape(c, h, w)
+    labels = torch.empty((b, h, w), dtype=torch.uint8, device=z.device)
+    top = q_out[:, :c_used].max(dim=1, keepdim=True).values
+    first = (q_out[:, :c_used] == top).to(torch.uint8).argmax(dim=1)  # the first maximum, as numpy's argmax
+    labels.copy_(first)
+    return q_out, labels
+
+
+def dense_crf(logits, rgb=None, n_iters=CRF_DEFAULTS["n_iters"], sxy_gaussian=CRF_DEFAULTS["sxy_gaussian"],
+              compat_gaussian=CRF_DEFAULTS["compat_gaussian"], sxy_bilateral=CRF_DEFAULTS["sxy_bilateral"],
+              compat_bilateral=CRF_DEFAULTS["compat_bilateral"], srgb_bilateral=CRF_DEFAULTS["srgb_bilateral"], c_used=None):
+    """tools/crf.py:14-60 with exact pairwise sums: fp32 logits [B,C,H,W] (what ``prob/<name>.npy`` holds) and,
+    for the bilateral term, a uint8 RGB batch [B,H,W,3] -> (Q^{n_iters} fp32 [B,C,H,W], labels uint8 [B,H,W] = the arg-max over the first
+    ``c_used`` classes, all by default, first maximum on a tie).  Inference only.  ``sxy`` are (x, y) as in pydensecrf; a single number
+    stands for both."""
+    if logits.requires_grad:
+        raise RuntimeError("mcdseg: dense_crf is inference only: the logits require grad")
+    z = _req(logits, "logits")
+    if z.dim() != 4 or z.numel() == 0:
+        raise TypeError("mcdseg: dense_crf takes non-empty fp32 logits [B,C,H,W]")
+    b, c, h, w = z.shape
+    if rgb is not None:
+        rgb = _req(rgb, "RGB batch", torch.uint8)
+        if tuple(rgb.shape) != (b, h, w, 3):
+            raise ValueError("mcdseg: dense_crf needs a uint8 RGB batch %s, got %s" % ((b, h, w, 3), tuple(rgb.shape)))
+    c_used = c if c_used is None else int(c_used)
+    params = (_pair(sxy_gaussian, 2, "sxy_gaussian") + (float(compat_gaussian),) + _pair(sxy_bilateral, 2, "sxy_bilateral") +
+              (float(compat_bilateral),) + _pair(srgb_bilateral, 3, "srgb_bilateral"))
+    L = lib()
+    nbytes = L.mcdseg_dense_crf_workspace_bytes(b, c, h, w, int(rgb is not None))
+    if not fused_crf():
+        # the same refusals as the library's, from the library: nothing is launched by a call with a null output
+        if not 1 <= c_used <= c or int(n_iters) < 0 or nbytes == 0 or min(params[:2]) <= 0 or (rgb is not None and min(params[3:5] + params[6:]) <= 0):
+            raise RuntimeError("mcdseg: dense_crf refuses these arguments (C_used in [1, C], n_iters >= 0, positive standard deviations)")
+        with torch.no_grad():
+            return _crf_composed(z, rgb, int(n_iters), params, c_used)
+    ws = _ws(nbytes, z.device)
+    q = torch.empty((b, c, h, w), dtype=torch.float32, device=z.device)
+    labels = torch.empty((b, h, w), dtype=torch.uint8, device=z.device)
+    host = (ctypes.c_float * 10)(*(params + (0.0,)))
+    n = h * w
+    with _timed("dense_crf", (2.0 * b * n * n * c * int(n_iters) * (rgb is not None), 16 * z.numel() * max(int(n_iters), 1))):
+        check(L.mcdseg_dense_crf(_p(z), _p(rgb), ctypes.cast(host, ctypes.c_void_p), _p(q), _p(labels), c_used, b, c, h, w, int(n_iters),
+                                 _p(ws), ctypes.c_size_t(nbytes), _stream()), "dense_crf")
+    return q, labels
+
+
 def confusion_hist_(hist, gt, pred):
     """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated.  An entry
     whose prediction lies outside [0, n) is dropped too: it is not binned into a neighbouring row, as the reference's
