@@ -737,7 +737,9 @@ int mcdseg_dense_crf(const float* logits, const uint8_t* rgb, const float* param
 int32_t mcdseg_conv_split_half_ok(const mcdseg_conv_desc* d, int32_t math, int32_t dgrad);
 /* Which kernels a call will launch, for profilers and bench.py's per-kernel tables (the host side derives rocprofv3's kernel names from
  * these instead of restating the dispatch): mcdseg_up8_loss_variant = the class count of mcdseg_up8_softmax_ce_l1's LDS-DMA instantiation
- * (16, 24, 41, 48) or minus that of the register-staged kernel; mcdseg_conv_wgrad_thin_tr_config = the template arguments
+ * (16, 24, 41, 48) or minus that of the register-staged kernel (labelled: 0 no labels, 1 labels at a 16-byte aligned address, 2 labels at
+ * an address that is only 8-byte aligned -- the LDS-DMA kernel fetches labels in 16-byte units, so those run the register-staged kernel);
+ * mcdseg_conv_wgrad_thin_tr_config = the template arguments
  * <cin8, mt, ntl, tr> of the thin layers' window weight gradient as cin8 * 1000000 + mt * 10000 + ntl * 100 + tr (0: not that kernel). */
 int32_t mcdseg_up8_loss_variant(int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t labelled);
 int32_t mcdseg_conv_wgrad_thin_tr_config(const mcdseg_conv_desc* d);

@@ -507,11 +507,16 @@ int launch_up_loss_dma(const char* entry, int kind, bool two, int blocks, hipStr
 // the instantiation of the DMA kernel for C classes: the benchmark's 41 has its own (no padding classes: 15 % less arithmetic)
 int up_loss_dma_ncmax(int C) { return C <= 16 ? 16 : (C <= 24 ? 24 : (C == 41 ? 41 : 48)); }
 
-bool up_loss_dma_ok(int64_t N, int64_t C, int64_t Hi, int64_t Wi, bool labels) {
+// labels: 0 none, 1 at a 16-byte aligned base, 2 at a base that is only 8-byte aligned (a contiguous view that starts at an odd element
+// of a larger int64 tensor).  The DMA kernel fetches labels as 16-byte units from base + a multiple of 16, and nothing establishes that
+// a 16-byte LDS-DMA from an address that is not 16-byte aligned is legal: such labels go to the register-staged kernel, which reads
+// them as single int64.
+bool up_loss_dma_ok(int64_t N, int64_t C, int64_t Hi, int64_t Wi, int labels) {
   const bool on = mcd_opt(MCD_OPT_UP8_LOSS_DMA) != 0;  // 0: the register-staged kernel (A/B, and the parity test's other side)
   // buffer resources address 32 bits (the DMA's offsets are formed in int)
-  return on && N * C * Hi * Wi * 4 < (1ll << 31) && (!labels || N * Hi * Wi * 64 * 8 < (1ll << 31));
+  return on && labels != 2 && N * C * Hi * Wi * 4 < (1ll << 31) && (!labels || N * Hi * Wi * 64 * 8 < (1ll << 31));
 }
+int up_loss_labels_kind(const int64_t* labels) { return labels == nullptr ? 0 : ((reinterpret_cast<uintptr_t>(labels) & 15) == 0 ? 1 : 2); }
 
 }  // namespace
 
@@ -643,7 +648,7 @@ static int up8_softmax_ce_any(const char* entry, int kind, const float* s1, cons
   }
   const double inv_m = 1.0 / ((double)P * (double)C);
   const bool two = s2 != nullptr;
-  if (up_loss_dma_ok(N, C, Hi, Wi, labels != nullptr)) {
+  if (up_loss_dma_ok(N, C, Hi, Wi, up_loss_labels_kind(labels))) {
     int rc;
 #define MCD_UP_DMA(NC)                                                                                                              \
   rc = (C == NC) ? launch_up_loss_dma<NC, true>(entry, kind, two, nblk, st, s1, w1, s2, w2, labels, class_weight, ignore_index, ce_coef, diff_coef, \
@@ -741,9 +746,10 @@ extern "C" int mcdseg_scale_by_device_scalar(float* buf, const float* scale, int
 
 // Which kernel mcdseg_up8_softmax_ce_l1 launches for a problem (profilers, bench.py's per-kernel tables): the class count of the LDS-DMA
 // kernel's instantiation (16, 24, 41, 48), or MINUS that of the register-staged kernel (16, 24, 48) when the option UP8_LOSS_DMA is 0
-// or a tensor outgrows a 32-bit buffer resource.
+// or a tensor outgrows a 32-bit buffer resource, or the labels start at an address that is not 16-byte aligned (labelled = 2; 1: labels at
+// an aligned base, 0: none).
 extern "C" int32_t mcdseg_up8_loss_variant(int32_t N, int32_t C, int32_t Hi, int32_t Wi, int32_t labelled) {
   if (N <= 0 || C <= 0 || Hi <= 0 || Wi <= 0) return 0;
-  if (up_loss_dma_ok(N, C, Hi, Wi, labelled != 0)) return up_loss_dma_ncmax(C);
+  if (up_loss_dma_ok(N, C, Hi, Wi, labelled == 2 ? 2 : (labelled != 0 ? 1 : 0))) return up_loss_dma_ncmax(C);
   return -(C <= 16 ? 16 : (C <= 24 ? 24 : 48));
 }

@@ -2381,10 +2381,15 @@ def mcd_losses(z1, z2, labels, class_weight, ignore_index=-100, ce_coef=0.0, dif
 def up8_loss_kernel_name(n, c, hi, wi, two, labelled, dist="diff"):
     """The kernel ``mcdseg_up8_softmax_ce_l1`` launches for this problem, as rocprofv3 prints it -- from the library's own dispatch
     (``mcdseg_up8_loss_variant``: the LDS-DMA kernel unless the option UP8_LOSS_DMA is 0 or a tensor outgrows a 32-bit buffer resource;
-    the benchmark's 41 classes have an instantiation of their own)."""
+    the benchmark's 41 classes have an instantiation of their own).  ``labelled``: whether the call has labels, or the label tensor itself
+    -- labels whose first element is not 16-byte aligned (a view into a larger tensor) run the register-staged kernel."""
     kind = dist_kind(dist)
     two = "true" if two else "false"
-    v = lib().mcdseg_up8_loss_variant(int(n), int(c), int(hi), int(wi), int(bool(labelled)))
+    if torch.is_tensor(labelled):
+        labelled = 1 if labelled.data_ptr() % 16 == 0 else 2
+    else:
+        labelled = int(bool(labelled))
+    v = lib().mcdseg_up8_loss_variant(int(n), int(c), int(hi), int(wi), labelled)
     if kind != 0:  # ``mcdseg_up8_softmax_ce_dist``: the same dispatch, kernels of their own (two heads always)
         if v > 0:
             return "up8_softmax_ce_dist_dma_kernel<%d, %s, %d>" % (v, "true" if c == v else "false", kind)
@@ -2428,12 +2433,12 @@ def up8_mcd_losses(s1, w1, s2, w2, labels, class_weight, ignore_index=-100, ce_c
     heads = 1 if s2 is None else 2
     byts = 4 * heads * n * c * h * w * (1 if want_grad else 0) + 4 * heads * n * c * hi * wi + (8 * n * h * w if labels is not None else 0)
     if kind != 0:
-        with _timed(up8_loss_kernel_name(n, c, hi, wi, True, labels is not None, kind), (0, byts)):
+        with _timed(up8_loss_kernel_name(n, c, hi, wi, True, labels, kind), (0, byts)):
             check(L.mcdseg_up8_softmax_ce_dist(_p(s1), _p(w1), _p(s2), _p(w2), _p(labels), _p(class_weight), int(ignore_index),
                                                float(ce_coef), float(diff_coef), _p(wsum), _p(g1), _p(g2), _p(losses), n, c, hi, wi, kind,
                                                _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()), "up8_softmax_ce_dist")
         return losses, g1, g2
-    with _timed(up8_loss_kernel_name(n, c, hi, wi, s2 is not None, labels is not None), (0, byts)):
+    with _timed(up8_loss_kernel_name(n, c, hi, wi, s2 is not None, labels), (0, byts)):
         check(L.mcdseg_up8_softmax_ce_l1(_p(s1), _p(w1), _p(s2), _p(w2), _p(labels), _p(class_weight), int(ignore_index),
                                          float(ce_coef), float(diff_coef), _p(wsum), _p(g1), _p(g2), _p(losses), n, c, hi, wi,
                                          _p(ws), ctypes.c_size_t(ws.numel() * 4), _stream()), "up8_softmax_ce_l1")

@@ -269,8 +269,9 @@ def test_up8_loss_fused_equals_two_pass(shape, mode, dma, monkeypatch, libopt):
     """The loss kernel that forms the up-sampled logits on the fly (mcdseg_up8_softmax_ce_l1) against up8 followed by the
     plain loss kernel: identical logit gradients (bitwise), loss values up to the order of the block partial sums; ragged
     row segments (8 Wi not a multiple of 128), the image border and ignore_index pixels included.  Both forms of the kernel:
-    inputs prefetched by LDS-DMA behind a counted wait (the default; the last two shapes give every workgroup several
-    patches, i.e. gradient stores still in flight when the next patch's inputs are waited for) and staged through registers."""
+    inputs prefetched by LDS-DMA behind a counted wait (the default; the last two shapes are 465 and 495 patches on 256 workgroups,
+    i.e. some workgroups take a second patch with gradient stores still in flight when its inputs are waited for -- none takes a third,
+    so no LDS buffer is refilled here: tests/test_loss_edges_gpu.py does that, against fp64) and staged through registers."""
     dev = _dev()
     from mcdseg import ops
     libopt(UP8_LOSS_DMA=int(dma))
