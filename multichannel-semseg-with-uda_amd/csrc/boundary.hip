@@ -66,20 +66,12 @@ __device__ __forceinline__ float boundary_at(const T* __restrict__ lab, int H, i
 
 // out[0] = loss = ((1 - beta) sum bce + (2 beta - 1) sum t bce) / n,  out[1] = beta = 1 - sum t / n
 __global__ __launch_bounds__(256) void bce_finalize_kernel(const double* __restrict__ part, int nblk, double n, float* __restrict__ out) {
-  double s[3] = {0.0, 0.0, 0.0};
-  for (int i = threadIdx.x; i < nblk; i += 256)
-    for (int k = 0; k < 3; ++k) s[k] += part[(size_t)i * 3 + k];
-  __shared__ double sh[3][4];
-  for (int k = 0; k < 3; ++k) {
-    const double v = wave_sum_d(s[k]);
-    if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = v;
-  }
-  __syncthreads();
+  double tot[3];
+  partials_total(part, nblk, 3, 0, tot);
   if (threadIdx.x == 0) {
-    double tot[3];
-    for (int k = 0; k < 3; ++k) tot[k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
-    const double beta = 1.0 - tot[0] / n;
-    out[0] = (float)(((1.0 - beta) * tot[1] + (2.0 * beta - 1.0) * tot[2]) / n);
+    double loss, beta;
+    balanced_bce(tot, n, loss, beta);
+    out[0] = (float)loss;
     out[1] = (float)beta;
   }
 }

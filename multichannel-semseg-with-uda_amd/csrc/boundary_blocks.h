@@ -2,7 +2,7 @@
 // upsample_bilinear2d, the sigmoid, the class-balanced BCE term and its gradient, and the fp64 block partials of its three sums.
 // fp contraction is off, so a kernel that calls these computes the very bits another kernel that calls them does.
 #pragma once
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -67,19 +67,17 @@ __device__ __forceinline__ void sums_add(Sums& s, float p, float t) {
 // block partials: [block][3] doubles (sum t, sum bce, sum t*bce)
 __device__ __forceinline__ void sums_store(const Sums& s, double* __restrict__ part) {
   __shared__ double sh[3][4];
-  const double a = wave_sum_d((double)s.t), b = wave_sum_d((double)s.b), c = wave_sum_d((double)s.tb);
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = a;
-    sh[1][threadIdx.x >> 6] = b;
-    sh[2][threadIdx.x >> 6] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x < 3) part[(size_t)blockIdx.x * 3 + threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
+  double v[3] = {(double)s.t, (double)s.b, (double)s.tb};
+  block_gather(v, sh);
+  if (threadIdx.x < 3) part[(size_t)blockIdx.x * 3 + threadIdx.x] = tree_total<4>(sh[threadIdx.x]);
 }
 
-int sum_blocks(int64_t n) {
-  const int64_t b = ceil_div64(n, 256 * 16);
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
+// the totals of those partials over n elements -> beta = 1 - sum t / n,  loss = ((1 - beta) sum bce + (2 beta - 1) sum t bce) / n
+__device__ __forceinline__ void balanced_bce(const double (&tot)[3], double n, double& loss, double& beta) {
+  beta = 1.0 - tot[0] / n;
+  loss = ((1.0 - beta) * tot[1] + (2.0 * beta - 1.0) * tot[2]) / n;
 }
+
+int sum_blocks(int64_t n) { return ceil_div64(n, 256 * 16, 2048); }
 
 }  // namespace

@@ -29,6 +29,11 @@ void mcdseg_set_error(const char* fmt, ...);
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// blocks of a grid-stride kernel: ceil(n / per_block) clamped to [1, cap]
+static inline int ceil_div64(int64_t n, int64_t per_block, int cap) {
+  const int64_t b = ceil_div64(n, per_block);
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 static inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 
 // ---- GEMM padding rules shared by pack / fprop / dgrad / wgrad -------------------------------

@@ -9,7 +9,7 @@
 //                dx = y*(dy - sum_c dy*y)
 //  prob_nll      loss = sum_i w[y_i]*(-log p[y_i]) / sum_i w[y_i]                (NLLLoss2d(log(p)), loss.py:30)
 //                dp[n,c,i] = (c == y_i) ? -w[y_i] / (p[y_i] * sum w) : 0
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -139,21 +139,17 @@ __global__ __launch_bounds__(256) void prob_nll_partial_kernel(const float* __re
     ls += (double)(w * -logf(pv));
     ws += (double)w;
   }
-  ls = wave_sum_d(ls);
-  ws = wave_sum_d(ws);
-  __shared__ double sl[4], sw[4];
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    sl[wave] = ls;
-    sw[wave] = ws;
-  }
-  __syncthreads();
+  __shared__ double sh[2][4];
+  double v[2] = {ls, ws};
+  block_gather(v, sh);
   if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = (sl[0] + sl[1]) + (sl[2] + sl[3]);
-    part[2 * blockIdx.x + 1] = (sw[0] + sw[1]) + (sw[2] + sw[3]);
+    part[2 * blockIdx.x] = tree_total<4>(sh[0]);
+    part[2 * blockIdx.x + 1] = tree_total<4>(sh[1]);
   }
 }
 
+// Adds the partial rows serially, in one thread: an order of its own, not partials_total's (block_reduce.h) -- routing it through the
+// helper would change the bits of the loss.
 __global__ void prob_nll_finalize_kernel(const double* __restrict__ part, int blocks, float* __restrict__ loss) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   double ls = 0.0, ws = 0.0;
@@ -185,12 +181,7 @@ __global__ __launch_bounds__(256) void prob_nll_grad_kernel(const float* __restr
   }
 }
 
-int stream_blocks(int64_t n) {
-  int64_t b = ceil_div64(n, 256 * 4);
-  if (b > 4096) b = 4096;
-  if (b < 1) b = 1;
-  return (int)b;
-}
+int stream_blocks(int64_t n) { return ceil_div64(n, 256 * 4, 4096); }
 
 }  // namespace
 

@@ -8,7 +8,8 @@
 // The interpolation expressions are restated from bilinear8_fwd_kernel (multitask.hip) and up8_fwd_kernel (up8.hip): the build
 // compiles with -ffp-contract=off, so the same expression in the same order gives the same bits, and the labels equal those of the
 // unfused composition bit for bit.
-#include "common.h"
+#include "block_reduce.h"
+#include "predict_pixel.h"
 
 namespace {
 
@@ -27,7 +28,7 @@ __device__ __forceinline__ void bl_index(int dst, int in_size, int& i0, int& i1,
 // One workgroup = one image n and one band b of output rows, [8b-4, 8b+4) clipped to [0, 8Hi), b = 0..Hi.  Every pixel of the band
 // reads input rows r0 = max(b-1, 0) and r0+1 (clamped) only, under either up-sampler: bilinear y0 = b-1 (0 in band 0), y1 = y0+1
 // clamped; learned iy = b and b-1 where they exist.  Those two rows of all C channels (and the C 16x16 kernels) are staged in LDS,
-// then each thread forms a pixel's C logits in registers and runs predict_kernel's softmax / argmax / entropy (loss.hip) on them.
+// then each thread forms a pixel's C logits in registers and runs predict_kernel's softmax / argmax / entropy (predict_pixel.h) on them.
 template <int NCMAX, bool LEARNED>
 __global__ __launch_bounds__(INF_NT) void predict_up8_kernel(const float* __restrict__ s, const float* __restrict__ w,
                                                              uint8_t* __restrict__ labels, float* __restrict__ part, int C, int C_used,
@@ -107,47 +108,14 @@ __global__ __launch_bounds__(INF_NT) void predict_up8_kernel(const float* __rest
         a[c] = v;
       }
     }
-    float m = a[0], mu = a[0];
-    int best = 0;
-#pragma unroll
-    for (int c = 1; c < NCMAX; ++c) {
-      m = fmaxf(m, a[c]);
-      if (c < C_used && a[c] > mu) {
-        mu = a[c];
-        best = c;
-      }
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCMAX; ++c) {
-      a[c] = (c < C) ? expf(a[c] - m) : 0.f;
-      sum += a[c];
-    }
-    const float r = 1.f / sum;
-#pragma unroll
-    for (int c = 0; c < NCMAX; ++c)
-      if (c < C) {
-        const float pc = a[c] * r;
-        ent += pc * logf(pc + 1e-6f);
-      }
+    int best;
+    MCD_PREDICT_PIXEL(a, best, ent)
     lab[p] = (uint8_t)best;
   }
-  __shared__ float sh[INF_NT / 64];
-  ent = wave_sum(ent);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = ent;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + (sh[2] + sh[3])) + ((sh[4] + sh[5]) + (sh[6] + sh[7]));
-}
-
-__global__ __launch_bounds__(256) void entropy_finalize_kernel(const float* __restrict__ part, int64_t nblk, double neg_inv_m,
-                                                               float* __restrict__ out) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < nblk; i += 256) s += (double)part[i];
-  __shared__ double sh[4];
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (float)(((sh[0] + sh[1]) + (sh[2] + sh[3])) * neg_inv_m);
+  __shared__ float sh[1][INF_NT / 64];
+  float v[1] = {ent};
+  block_gather(v, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = tree_total<INF_NT / 64>(sh[0]);
 }
 
 // np.uint8(t) for a float64 t as numpy does it on x86-64: the C cast (npy_ubyte)t, compiled as a truncating conversion to int32
@@ -234,7 +202,7 @@ extern "C" int mcdseg_predict_labels_up8(const float* s, const float* w, uint8_t
   if (rc != 0) return rc;
   MCD_LAUNCH_CHECK("predict_labels_up8");
   const double P = (double)N * Hi * Wi * 64;
-  hipLaunchKernelGGL(entropy_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)part, (int64_t)blocks, -1.0 / (P * (double)C),
+  hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(1), dim3(256), 0, st, (const float*)part, (int64_t)blocks, -1.0 / (P * (double)C),
                      entropy);
   MCD_LAUNCH_CHECK("predict_labels_up8 (finalize)");
   return 0;

@@ -13,7 +13,8 @@
 // (2C reads + 2C writes) * 4 B + 8 B label per pixel; everything else stays in registers.
 #include <stdlib.h>
 
-#include "common.h"
+#include "block_reduce.h"
+#include "predict_pixel.h"
 
 namespace {
 
@@ -26,21 +27,10 @@ __global__ __launch_bounds__(256) void label_wsum_kernel(const int64_t* __restri
     const int64_t y = labels[i];
     if (y != ignore_index && y >= 0 && y < C) s += cw ? cw[y] : 1.f;
   }
-  __shared__ float sh[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__global__ __launch_bounds__(256) void wsum_finalize_kernel(const float* __restrict__ part, int n, float* __restrict__ out) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < n; i += 256) s += (double)part[i];
-  __shared__ double sh[4];
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (float)((sh[0] + sh[1]) + (sh[2] + sh[3]));
+  __shared__ float sh[1][4];
+  float v[1] = {s};
+  block_gather(v, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = tree_total<4>(sh[0]);
 }
 
 // The per-pixel maths shared by the two front ends below: a[] / b[] hold the pixel's logits (-inf past C) and leave as its
@@ -330,6 +320,8 @@ struct UpDmaLayout {
 // and the reference's weighted mean is 0/0: nn.NLLLoss2d returns NaN and NaN gradients (loss.py:7-13).  The kernel does the
 // same -- value here, gradients through kce = ce_coef * w[y] / W in the main kernel -- so the failure is as visible as in
 // the reference instead of a healthy-looking 0 in the log while NaN gradients reach the optimizer.
+// The sums are partials_total<3> (block_reduce.h) written out: this kernel runs in every training step and is held to the instruction
+// stream it always had, which the call does not reproduce (the LDS rows reach the helper as generic pointers and are scheduled anew).
 __global__ __launch_bounds__(256) void loss_finalize_kernel(const float* __restrict__ part, int64_t nblk, float* __restrict__ losses,
                                                             double inv_m, int has_ce) {
   double s[3] = {0.0, 0.0, 0.0};
@@ -377,47 +369,14 @@ __global__ __launch_bounds__(256) void predict_kernel(const float* __restrict__ 
       }
       a[c] = v;
     }
-    float m = a[0], mu = a[0];
-    int best = 0;
-#pragma unroll
-    for (int c = 1; c < NCMAX; ++c) {
-      m = fmaxf(m, a[c]);
-      if (c < C_used && a[c] > mu) {
-        mu = a[c];
-        best = c;
-      }
-    }
-    float s = 0.f;
-#pragma unroll
-    for (int c = 0; c < NCMAX; ++c) {
-      a[c] = (c < C) ? expf(a[c] - m) : 0.f;
-      s += a[c];
-    }
-    const float r = 1.f / s;
-#pragma unroll
-    for (int c = 0; c < NCMAX; ++c)
-      if (c < C) {
-        const float pc = a[c] * r;
-        ent += pc * logf(pc + 1e-6f);
-      }
+    int best;
+    MCD_PREDICT_PIXEL(a, best, ent)
     labels[pix] = (uint8_t)best;
   }
-  __shared__ float sh[4];
-  ent = wave_sum(ent);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = ent;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-__global__ __launch_bounds__(256) void predict_finalize_kernel(const float* __restrict__ part, int64_t nblk, double neg_inv_m,
-                                                               float* __restrict__ out) {
-  double s = 0.0;
-  for (int64_t i = threadIdx.x; i < nblk; i += 256) s += (double)part[i];
-  __shared__ double sh[4];
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (float)(((sh[0] + sh[1]) + (sh[2] + sh[3])) * neg_inv_m);
+  __shared__ float sh[1][4];
+  float v[1] = {ent};
+  block_gather(v, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = tree_total<4>(sh[0]);
 }
 
 __global__ void scale_by_device_scalar_kernel(float* __restrict__ buf, const float* __restrict__ scale, int64_t n4, int64_t n) {
@@ -431,10 +390,7 @@ __global__ void scale_by_device_scalar_kernel(float* __restrict__ buf, const flo
   for (int64_t i = n4 * 4 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) buf[i] *= s;
 }
 
-int wsum_blocks(int64_t P) {
-  const int64_t b = ceil_div64(P, 256 * 8);
-  return (int)(b < 1 ? 1 : (b > 1024 ? 1024 : b));
-}
+int wsum_blocks(int64_t P) { return ceil_div64(P, 256 * 8, 1024); }
 
 template <int NCMAX>
 void launch_loss(int kind, bool two, dim3 grid, hipStream_t st, const float* z1, const float* z2, const int64_t* labels, const float* cw,
@@ -536,7 +492,7 @@ extern "C" int mcdseg_label_weight_sum(const int64_t* labels, const float* class
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(label_wsum_kernel, dim3(wb), dim3(256), 0, st, labels, class_weight, ignore_index, C, P, (float*)workspace);
   MCD_LAUNCH_CHECK("label_wsum");
-  hipLaunchKernelGGL(wsum_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, wb, out);
+  hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(1), dim3(256), 0, st, (const float*)workspace, (int64_t)wb, 1.0, out);
   MCD_LAUNCH_CHECK("wsum_finalize");
   return 0;
 }
@@ -564,7 +520,7 @@ static int softmax_ce_any(const char* entry, int kind, const float* z1, const fl
   } else if (labels != nullptr) {
     hipLaunchKernelGGL(label_wsum_kernel, dim3(wb), dim3(256), 0, st, labels, class_weight, ignore_index, C, P, wpart);
     MCD_LAUNCH_CHECK("label_wsum");
-    hipLaunchKernelGGL(wsum_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)wpart, wb, losses + 3);
+    hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(1), dim3(256), 0, st, (const float*)wpart, (int64_t)wb, 1.0, losses + 3);
     MCD_LAUNCH_CHECK("wsum_finalize");
   } else {
     (void)hipMemsetAsync(losses + 3, 0, sizeof(float), st);
@@ -641,7 +597,7 @@ static int up8_softmax_ce_any(const char* entry, int kind, const float* s1, cons
   } else if (labels != nullptr) {
     hipLaunchKernelGGL(label_wsum_kernel, dim3(wb), dim3(256), 0, st, labels, class_weight, ignore_index, C, P, wpart);
     MCD_LAUNCH_CHECK("label_wsum");
-    hipLaunchKernelGGL(wsum_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)wpart, wb, losses + 3);
+    hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(1), dim3(256), 0, st, (const float*)wpart, (int64_t)wb, 1.0, losses + 3);
     MCD_LAUNCH_CHECK("wsum_finalize");
   } else {
     (void)hipMemsetAsync(losses + 3, 0, sizeof(float), st);
@@ -727,7 +683,7 @@ extern "C" int mcdseg_predict_labels(const float* z1, const float* z2, uint8_t* 
   else
     hipLaunchKernelGGL(predict_kernel<48>, dim3((unsigned)nblk), dim3(LOSS_BLOCK), 0, st, z1, z2, labels, (float*)workspace, C, C_used, HW, P);
   MCD_LAUNCH_CHECK("predict_labels");
-  hipLaunchKernelGGL(predict_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, nblk, -1.0 / ((double)P * (double)C), entropy);
+  hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(1), dim3(256), 0, st, (const float*)workspace, nblk, -1.0 / ((double)P * (double)C), entropy);
   MCD_LAUNCH_CHECK("predict_finalize");
   return 0;
 }

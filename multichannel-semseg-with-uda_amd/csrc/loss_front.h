@@ -40,18 +40,11 @@ __global__ __launch_bounds__(256) void MCD_FRONT_PLAIN(const float* __restrict__
     MCD_FRONT_PIXEL(a, b, y, wy, ce_coef, diff_coef, losses_w, g1, g2, base, (size_t)HW, C, inv_m, ce1, ce2, dsum);
   }
   __shared__ float sh[3][4];
-  ce1 = wave_sum(ce1);
-  ce2 = wave_sum(ce2);
-  dsum = wave_sum(dsum);
-  if ((threadIdx.x & 63) == 0) {
-    sh[0][threadIdx.x >> 6] = ce1;
-    sh[1][threadIdx.x >> 6] = ce2;
-    sh[2][threadIdx.x >> 6] = dsum;
-  }
-  __syncthreads();
+  float v[3] = {ce1, ce2, dsum};
+  block_gather(v, sh);
   if (threadIdx.x < 3) {
     const int q = threadIdx.x;
-    part[(size_t)blockIdx.x * 3 + q] = (sh[q][0] + sh[q][1]) + (sh[q][2] + sh[q][3]);
+    part[(size_t)blockIdx.x * 3 + q] = tree_total<4>(sh[q]);
   }
 }
 
@@ -127,20 +120,11 @@ __global__ __launch_bounds__(UP_NT) void MCD_FRONT_UP8(const float* __restrict__
     }
   }
   __shared__ float sh[3][UP_NT / 64];
-  ce1 = wave_sum(ce1);
-  ce2 = wave_sum(ce2);
-  dsum = wave_sum(dsum);
-  if (lane == 0) {
-    sh[0][ky0] = ce1;
-    sh[1][ky0] = ce2;
-    sh[2][ky0] = dsum;
-  }
-  __syncthreads();
+  float v[3] = {ce1, ce2, dsum};
+  block_gather(v, sh);
   if (threadIdx.x < 3) {
     const int q = threadIdx.x;
-    float t = 0.f;
-    for (int k = 0; k < UP_NT / 64; ++k) t += sh[q][k];
-    part[(size_t)blockIdx.x * 3 + q] = t;
+    part[(size_t)blockIdx.x * 3 + q] = chain_total<UP_NT / 64>(sh[q]);
   }
 }
 
@@ -271,6 +255,8 @@ __global__ __launch_bounds__(UP_NT) void MCD_FRONT_DMA(const float* __restrict__
       }
     }
   }
+  // block_gather + chain_total (block_reduce.h) written out: through the call, the two-head 24-class instantiations of this kernel come
+  // out with two instructions in another order, and the kernels of the training step keep the instruction stream they had
   __shared__ float sh[3][UP_NT / 64];
   ce1 = wave_sum(ce1);
   ce2 = wave_sum(ce2);

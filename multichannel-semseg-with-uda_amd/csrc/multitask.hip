@@ -3,7 +3,7 @@
 //                                                    models/dilated_fcn.py:676, 684-695)
 //   mean-squared error with its gradient             (F.mse_loss, models/dilated_fcn.py:712-714)
 // Both are HBM-bound streaming kernels on the full-resolution tensor.
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -107,27 +107,13 @@ __global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ p, c
     s += d * d;
     if (grad) grad[i] = d * gscale;
   }
-  __shared__ float sh[4];
-  s = wave_sum(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __shared__ float sh[1][4];
+  float v[1] = {s};
+  block_gather(v, sh);
+  if (threadIdx.x == 0) part[blockIdx.x] = tree_total<4>(sh[0]);
 }
 
-__global__ __launch_bounds__(256) void mse_finalize_kernel(const float* __restrict__ part, int nblk, double inv_n, float* __restrict__ out) {
-  double s = 0.0;
-  for (int i = threadIdx.x; i < nblk; i += 256) s += (double)part[i];
-  __shared__ double sh[4];
-  s = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) *out = (float)(((sh[0] + sh[1]) + (sh[2] + sh[3])) * inv_n);
-}
-
-int mse_blocks(int64_t n) {
-  const int64_t b = ceil_div64(n, 256 * 16);
-  return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b));
-}
+int mse_blocks(int64_t n) { return ceil_div64(n, 256 * 16, 2048); }
 
 }  // namespace
 
@@ -161,7 +147,7 @@ extern "C" int mcdseg_mse(const float* pred, const float* target, float* grad, f
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(mse_kernel, dim3(nb), dim3(256), 0, st, pred, target, grad, (float*)workspace, n4, n, (float)(2.0 / (double)n));
   MCD_LAUNCH_CHECK("mse");
-  hipLaunchKernelGGL(mse_finalize_kernel, dim3(1), dim3(256), 0, st, (const float*)workspace, nb, 1.0 / (double)n, loss);
+  hipLaunchKernelGGL(sum_finalize_kernel<float>, dim3(1), dim3(256), 0, st, (const float*)workspace, (int64_t)nb, 1.0 / (double)n, loss);
   MCD_LAUNCH_CHECK("mse_finalize");
   return 0;
 }

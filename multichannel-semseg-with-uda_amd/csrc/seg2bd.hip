@@ -108,30 +108,22 @@ __global__ __launch_bounds__(256) void seg2bd_fwd_kernel(const float* __restrict
   sums_store(s, part + (size_t)head * gridDim.x * 3);
 }
 
-// out[0], out[1] = the two heads' losses (out[1] = 0 with one head), out[2] = beta = 1 - sum t / n; bce_finalize_kernel per head
+// out[0], out[1] = the two heads' losses (out[1] = 0 with one head), out[2] = beta = 1 - sum t / n; bce_finalize_kernel (boundary.hip) per head
 __global__ __launch_bounds__(256) void seg2bd_finalize_kernel(const double* __restrict__ part, int nblk, int heads, double n, float* __restrict__ out) {
-  __shared__ double sh[3][4];
   for (int h = 0; h < 2; ++h) {
     if (h >= heads) {
       if (threadIdx.x == 0) out[h] = 0.f;
       continue;
     }
-    double s[3] = {0.0, 0.0, 0.0};
-    for (int i = threadIdx.x; i < nblk; i += 256)
-      for (int k = 0; k < 3; ++k) s[k] += part[((size_t)h * nblk + i) * 3 + k];
-    for (int k = 0; k < 3; ++k) {
-      const double t = wave_sum_d(s[k]);
-      if ((threadIdx.x & 63) == 0) sh[k][threadIdx.x >> 6] = t;
-    }
-    __syncthreads();
+    double tot[3];
+    partials_total(part + (size_t)h * nblk * 3, nblk, 3, 0, tot);
     if (threadIdx.x == 0) {
-      double tot[3];
-      for (int k = 0; k < 3; ++k) tot[k] = (sh[k][0] + sh[k][1]) + (sh[k][2] + sh[k][3]);
-      const double beta = 1.0 - tot[0] / n;
-      out[h] = (float)(((1.0 - beta) * tot[1] + (2.0 * beta - 1.0) * tot[2]) / n);
+      double loss, beta;
+      balanced_bce(tot, n, loss, beta);
+      out[h] = (float)loss;
       if (h == 0) out[2] = (float)beta;
     }
-    __syncthreads();
+    __syncthreads();  // the second head reuses the LDS slots
   }
 }
 
@@ -152,11 +144,10 @@ __global__ __launch_bounds__(256) void seg2bd_dv_kernel(const float* __restrict_
     g[(size_t)head * total + idx] = d;
     sum += d;
   }
-  __shared__ double sh[4];
-  const double a = wave_sum_d((double)sum);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) part[(size_t)head * gridDim.x + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  __shared__ double sh[1][4];
+  double a[1] = {(double)sum};
+  block_gather(a, sh);
+  if (threadIdx.x == 0) part[(size_t)head * gridDim.x + blockIdx.x] = tree_total<4>(sh[0]);
 }
 
 // T[head][n][k][iy,ix] = sum over the up-sampled pixels (oy, ox) low-resolution pixel (iy, ix) feeds -- rows / columns [8 i - 4, 8 i + 12)
@@ -271,13 +262,9 @@ __global__ __launch_bounds__(256) void seg2bd_dw_finalize_kernel(const double* _
     dw[pair] = (float)s;
     return;
   }
-  double s = 0.0;
-  for (int i = threadIdx.x; i < ndb; i += 256) s += db_part[i];
-  __shared__ double sh[4];
-  const double a = wave_sum_d(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-  __syncthreads();
-  if (threadIdx.x == 0) db[0] = (float)((sh[0] + sh[1]) + (sh[2] + sh[3]));
+  double tot[1];
+  partials_total(db_part, ndb, 1, 0, tot);
+  if (threadIdx.x == 0) db[0] = (float)tot[0];
 }
 
 bool seg2bd_args_ok(int N, int C, int Hi, int Wi) {

@@ -25,7 +25,7 @@
 // of each draw -- 2 C exponentials beside 2 C four-byte stores per pixel -- and accumulates GU and GV.  No tensor with a T
 // dimension exists.  Loss values: per-lane sums over the lane's pixels, one partial per workgroup, fp64 in the finalize launch; no
 // atomics, so results are bit-reproducible.
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -222,18 +222,11 @@ __global__ __launch_bounds__(UP_NT) void up8_uncertain_kernel(const float* __res
   }
   if (BWD) return;  // (uniform: the backward launch has no partial sums)
   __shared__ float sh[2][UP_NT / 64];
-  bsum = wave_sum(bsum);
-  usum = wave_sum(usum);
-  if (lane == 0) {
-    sh[0][ky0] = bsum;
-    sh[1][ky0] = usum;
-  }
-  __syncthreads();
+  float sums[2] = {bsum, usum};
+  block_gather(sums, sh);
   if (threadIdx.x < 2) {
     const int q = threadIdx.x;
-    float t = 0.f;
-    for (int k = 0; k < UP_NT / 64; ++k) t += sh[q][k];
-    part[((size_t)ns * gridDim.x + blockIdx.x) * 2 + q] = t;
+    part[((size_t)ns * gridDim.x + blockIdx.x) * 2 + q] = chain_total<UP_NT / 64>(sh[q]);
   }
 }
 
@@ -243,14 +236,10 @@ __global__ __launch_bounds__(256) void uncertain_finalize_kernel(const float* __
   const int b = blockIdx.x;
   const int q = b < N ? 1 : 0;
   const int64_t first = b < N ? (int64_t)b * gx : 0, count = b < N ? gx : (int64_t)N * gx;
-  double sum = 0.0;
-  for (int64_t i = threadIdx.x; i < count; i += 256) sum += (double)part[(first + i) * 2 + q];
-  __shared__ double sh[4];
-  sum = wave_sum_d(sum);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = sum;
-  __syncthreads();
+  double tot[1];
+  partials_total(part + first * 2, count, 2, q, tot);
   if (threadIdx.x == 0) {
-    const double v = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    const double v = tot[0];
     if (b < N)
       losses[2 + b] = (float)(v * lam_hw);
     else

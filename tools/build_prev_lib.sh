@@ -12,7 +12,7 @@ for f in $(git ls-tree -r --name-only "$REV" $P | grep -E "\.(h|hip)$"); do git 
 SKIP=""
 for f in "$@"; do
   NOPK=""
-  case "$f" in bn|loss|multitask|fusion|io|sgd|up8) NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops";; esac
+  case "$f" in bn|loss|multitask|fusion|io|sgd|adam|up8|infer|boundary|seg2bd|augment|uncertain|dann|join|unet|crf) NOPK="-Xclang -target-feature -Xclang -packed-fp32-ops";; esac
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -fvisibility=hidden $NOPK -I include -I "$T" -c "$T/$f.hip" -o "$T/$f.o" 2> /dev/null &
   SKIP="$SKIP|/$f.o"
 done
