@@ -717,6 +717,37 @@ size_t mcdseg_dense_crf_workspace_bytes(int32_t B, int32_t C, int32_t H, int32_t
 int mcdseg_dense_crf(const float* logits, const uint8_t* rgb, const float* params, float* q, uint8_t* labels, int32_t C_used, int32_t B,
                      int32_t C, int32_t H, int32_t W, int32_t n_iters, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Depth -> HHA, the input encoding of every 6-channel path (horizontal disparity, height above ground, angle with gravity: Gupta,
+ * Girshick, Arbelaez, Malik, ECCV 2014: saveHHA, processDepthImage, computeNormalsSquareSupport, getYDir) on the device
+ * (csrc/hha.hip).  The procedure of DESIGN.md section 4.13 is the definition and tests/hha_ref.py its fp64 statement; nothing is
+ * claimed about byte equality with the MATLAB release.  Per image, pixel (v, u) = (row, column), 0-based:
+ *   Z = depth_cm (missing where <= 0 or not finite); a = (u - cx)/fx, b = (v - cy)/fy, P = (aZ, bZ, Z), q = 100/Z;
+ *   normals for R = 3 and R = 10: a^2 ab a b^2 b 1 | aq bq q (0 at a missing pixel) summed over [v-R, v+R] x [u-R, u+R] clipped to the
+ *   image -> M, t; n = adj(M) t; N = n/|n| with N_z >= 0; (0,0,0) where the window holds fewer than 3 valid pixels or |n| is 0 or not
+ *   finite -- 0 meaning |n| <= 1e-14 max(sum a^2, sum b^2, count)^2 max|t|: valid pixels on one line leave only fp64 rounding noise
+ *   (below 1e-15 of that scale).  The constant is meant for fx, fy up to about 1000 pixels: three adjacent pixels not on one line lie at
+ *   6e-13 of the scale at fx = 520, 3e-14 at 1050 and reach 1e-14 at 1400, beyond which such a window counts as degenerate as well;
+ *   g from the R = 10 normals: (0,1,0), then 5 iterations at 45 degrees and 5 at 15: F = {|g.N| > cos}, W = {|g.N| < sin},
+ *   A = sum_W N N^T - sum_F N N^T, g' = the unit eigenvector of A's smallest eigenvalue with g.g' >= 0 (g stays when both sets are empty);
+ *   h = -g.P - y_min, y_min = the smallest -g.P of a valid pixel, or -130 where that is > -90;
+ *   bytes 31000/max(Z,100) | h | acosd(clamp(N3.g, -1, 1)) + 38 (0 where N3 is invalid), rounded half away from zero, saturated to [0,255].
+ *   depth_cm  fp32 [N,H,W] centimetres, 4-byte aligned;
+ *   camera    fp32 [N][4] = fx fy cx cy per image, ON THE HOST (read before the call returns; fx and fy are checked there);
+ *   hha       uint8 [N,H,W,3] in the order disparity, height, angle; a missing pixel is (0,0,0);
+ *   normals3  fp32 [N,H,W,3], the R = 3 normals (at missing pixels too), may be NULL;  gravity fp32 [N][3], may be NULL;
+ *   height    fp32 [N,H,W], h before rounding, 0 at a missing pixel, may be NULL.
+ * fp64 arithmetic throughout (the optional outputs are rounded once), no atomics, every sum in an order that depends on H and W alone:
+ * the same bits run to run, beside another process, and for an image alone or in a batch.  g stays on the device: the ten iterations
+ * run without a host synchronisation.
+ * -EINVAL before anything is launched: a null depth, camera, hha or workspace; a dimension < 1; N > 65535 (one image per grid row);
+ * H*W > 2^24 or N*H*W*3 >= 2^31 (what the index arithmetic covers); fx or fy not positive and finite, cx or cy not finite; a workspace
+ * smaller than mcdseg_depth_to_hha_workspace_bytes (the cameras, g and y_min in fp64, the block partials, and both normal maps in
+ * fp64: 48 bytes per pixel; each part padded to 256 bytes; 0 for dims that are refused) or not 16-byte aligned; an output or the
+ * depth not 4-byte aligned. */
+size_t mcdseg_depth_to_hha_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int mcdseg_depth_to_hha(const float* depth_cm, const float* camera, uint8_t* hha, float* normals3, float* gravity, float* height, int32_t N,
+                        int32_t H, int32_t W, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2-byte activation storage (round 6): BASELINE config 5 ("drn_d_105 ... bf16 ... HBM-bound stress"; the network is the reference's
  * Bottleneck trunk, models/drn.py:62-100, 344-348, trained by adapt_trainer.py:155-220).  In the one-term arithmetic MCDSEG_MATH_F16X1

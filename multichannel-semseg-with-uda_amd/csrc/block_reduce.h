@@ -12,7 +12,9 @@
 //                  sums_store: bce2d / boundary_head_bce / seg2bd forward (fp64)                             (boundary_blocks.h)
 //                  seg2bd_dv_kernel (fp64)                                                                   (seg2bd.hip)
 //                  prob_nll_partial_kernel (fp64)                                                            (fusion.hip)
-//                  and every finalizer, through partials_total (loss_finalize_kernel: the same steps written out).
+//                  hha_gravity_partial_kernel (fp64, twelve sums)                                            (hha.hip)
+//                  and every finalizer, through partials_total (loss_finalize_kernel: the same steps written out;
+//                  hha_gravity_final_kernel: twelve columns, then the eigen-step in thread 0).
 //   chain_total  left to right from zero, ((0 + r0) + r1) + ...; the zero stays: 0.f + -0.f is +0.f:
 //                  up8_softmax_ce_l1_kernel, up8_softmax_ce_dist_kernel                                      (loss_front.h)
 //                  up8_softmax_ce_l1_dma_kernel, up8_softmax_ce_dist_dma_kernel (the same steps written out) (loss_front.h)

@@ -202,6 +202,11 @@ class DeviceInputPipeline(object):
             off += p.shape[3]
         return out
 
+    def hha(self, depth, camera, unit_m=None):
+        """the HHA part of a depth batch [N,H,W] (``ops.depth_to_hha``: DESIGN.md section 4.13), uint8 [N,H,W,3] on the device:
+        ``images(rgb_u8, pipeline.hha(depth, camera, unit_m))`` is the whole 6-channel input path"""
+        return self._ops.depth_to_hha(depth.to(self.device, non_blocking=True), camera, unit_m)
+
     def labels(self, lbl_u8, params=None):
         lbl_u8 = lbl_u8.to(self.device, non_blocking=True)
         if self.joint_transform is not None:

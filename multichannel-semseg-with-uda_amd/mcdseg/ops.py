@@ -3045,6 +3045,54 @@ def dense_crf(logits, rgb=None, n_iters=CRF_DEFAULTS["n_iters"], sxy_gaussian=CR
     return q, labels
 
 
+# ------------------------------------------------------------------------------------------------ depth -> HHA
+def _hha_cameras(camera, n):
+    """one (fx, fy, cx, cy) or [N,4] -> a host array of n x 4 floats (the library reads the cameras on the host)"""
+    cam = torch.as_tensor(camera, dtype=torch.float32, device="cpu").reshape(-1)
+    if cam.numel() == 4:
+        cam = cam.repeat(n)
+    if cam.numel() != 4 * n:
+        raise ValueError("mcdseg: depth_to_hha takes one camera (fx, fy, cx, cy) or [N,4] = [%d,4], got %d values" % (n, cam.numel()))
+    return (ctypes.c_float * (4 * n))(*cam.tolist())
+
+
+def depth_to_hha(depth, camera, unit_m=None, return_parts=False):
+    """Depth -> HHA: ``depth`` [N,H,W] on the GPU, fp32 in centimetres (``unit_m`` None) or uint16 / int32 / fp32
+    in units of ``unit_m`` metres (0.001 for NYU and Kinect PNGs), converted by ONE fp32 multiply, ``depth.float() * (100 * unit_m)``;
+    a value <= 0 or not finite is missing.  ``camera``: one (fx, fy, cx, cy) in pixels for the batch, or [N,4].  Returns the uint8 batch
+    [N,H,W,3] (disparity, height, angle; (0,0,0) at a missing pixel) -- a part ``DeviceInputPipeline.images`` takes as it is -- and with
+    ``return_parts`` also a dict of what it was rounded from: ``normals3`` fp32 [N,H,W,3], ``gravity`` fp32 [N,3], ``height`` fp32 [N,H,W]."""
+    if not torch.is_tensor(depth) or depth.dim() != 3 or depth.numel() == 0:
+        raise TypeError("mcdseg: depth_to_hha takes a non-empty depth batch [N,H,W]")
+    if depth.dtype not in (torch.uint16, torch.int32, torch.float32):
+        raise TypeError("mcdseg: depth_to_hha takes uint16, int32 or fp32 depth, got %s" % depth.dtype)
+    if not depth.is_cuda:
+        raise RuntimeError("mcdseg: the depth batch must live on the GPU -- the HIP kernels are the only implementation (no CPU fallback)")
+    if unit_m is None:
+        if depth.dtype != torch.float32:
+            raise TypeError("mcdseg: depth_to_hha needs unit_m (metres per unit) for %s depth" % depth.dtype)
+        z = _req(depth, "depth batch")
+    else:
+        z = _req(depth.float() * (100 * float(unit_m)), "depth batch")  # (a permuted batch keeps its strides through the multiply)
+    n, h, w = z.shape
+    host = _hha_cameras(camera, n)
+    L = lib()
+    nbytes = L.mcdseg_depth_to_hha_workspace_bytes(n, h, w)
+    ws = _ws64(nbytes, z.device)
+    out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=z.device)
+    parts = None
+    if return_parts:
+        parts = {"normals3": torch.empty((n, h, w, 3), dtype=torch.float32, device=z.device),
+                 "gravity": torch.empty((n, 3), dtype=torch.float32, device=z.device),
+                 "height": torch.empty((n, h, w), dtype=torch.float32, device=z.device)}
+    with _timed("depth_to_hha", (600.0 * z.numel(), 110 * z.numel())):
+        check(L.mcdseg_depth_to_hha(_p(z), ctypes.cast(host, ctypes.c_void_p), _p(out), _p(parts and parts["normals3"]),
+                                    _p(parts and parts["gravity"]), _p(parts and parts["height"]), n, h, w, _p(ws),
+                                    ctypes.c_size_t(nbytes), _stream()), "depth_to_hha")
+    _on_launch_stream(z, ws, out, *(parts.values() if parts else ()))
+    return (out, parts) if return_parts else out
+
+
 def confusion_hist_(hist, gt, pred):
     """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated.  An entry
     whose prediction lies outside [0, n) is dropped too: it is not binned into a neighbouring row, as the reference's
