@@ -748,6 +748,47 @@ size_t mcdseg_depth_to_hha_workspace_bytes(int32_t N, int32_t H, int32_t W);
 int mcdseg_depth_to_hha(const float* depth_cm, const float* camera, uint8_t* hha, float* normals3, float* gravity, float* height, int32_t N,
                         int32_t H, int32_t W, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Ensembling of saved predictions (tools/ensemble_predict_from_npy.py:17-56 ensemble_predict) on the device (csrc/ensemble.hip;
+ * DESIGN.md section 4.14).  All of it is exact: fp32 additions in a stated order, one division, comparisons, integer gathers.
+ *
+ * mcdseg_ensemble_probs: K maps of the same N images, combined per element and arg-maxed per pixel in one pass.
+ *   maps     K device pointers ON THE HOST (read before the call returns), each fp32 [N][C][H][W], 4-byte aligned: the K uploads as they
+ *            stand, no [K,C,H,W] copy is made.  2 <= K <= MCDSEG_ENSEMBLE_MAX_K (16: the pointers travel as a kernel argument);
+ *   method   MCDSEG_ENSEMBLE_AVERAGING: sum(probs) / len(probs) as numpy evaluates it (:24): ((0 + p0) + p1) + ... left to right in fp32
+ *            -- the leading integer 0 is Python's, so a -0.0 leaves as +0.0 -- then ONE correctly rounded fp32 division by K: no
+ *            reciprocal, no contraction;
+ *            MCDSEG_ENSEMBLE_NMS: np.max(probs, 0) (:26): m = m > p ? m : p left to right (of +0 and -0 the later one stays, as in
+ *            numpy's maximum); a NaN in any map wins;
+ *            a NaN result of either leaves as 0x7FC00000 whatever its inputs' payloads were (IEEE leaves the payload of a NaN that an
+ *            addition makes to the implementation: numpy's is the host's, 0xFFC00000 on x86).  This holds for NMS too, where numpy
+ *            only hands an input NaN through: the payload and sign of an INPUT NaN are NOT preserved under either method;
+ *   out      fp32 [N][C][H][W], the combined map, or NULL: nothing is stored and only the first n_used classes are formed, in registers;
+ *   labels   uint8 [N][H][W] = argmax over c < n_used of out[c] by numpy's rule (:32): the first maximum wins, a NaN counts as the
+ *            maximum and the first NaN wins, +0 and -0 are equal.
+ * Four pixels per thread in 16-byte accesses when W % 4 == 0 and every pointer (maps, out, labels) is 16-byte aligned, one pixel per thread
+ * otherwise: the same bits.  Plain stores, no atomics: the same bits run to run, for an image alone or in a batch.
+ * -EINVAL before anything is launched: a null maps, map or labels; K outside [2, 16]; an unknown method; a dimension < 1; N > 65535;
+ * n_used outside [1, min(C, 256)]; H*W >= 2^31 or N*C*H*W >= 2^40; a map or out not 4-byte aligned.
+ *
+ * mcdseg_label_resize_colorize: Image.resize((OW, OH), NEAREST) of the label map (:33-35) and of its palette image (:43-56) as one gather.
+ *   labels     uint8 [N][H][W];  palette uint8 [n_pal][3] in device memory, 1 <= n_pal <= 256 (needed only with vis_out);
+ *   label_out  uint8 [N][OH][OW] = labels[iy[y]][ix[x]], ix / iy being Pillow's NEAREST source indices -- the rule of
+ *              mcdseg_resize_nearest_u8, computed by the same kernel -- may be NULL;
+ *   vis_out    uint8 [N][OH][OW][3] = palette[label_out], (0,0,0) for a label >= n_pal (Colorize.__call__, transform.py:155-165), may be
+ *              NULL (not both).
+ * -EINVAL before anything is launched: a null labels or workspace; no output; vis_out without a palette of 1..256 colours; a dimension
+ * < 1; N*H*W or N*OH*OW >= 2^40; a workspace smaller than mcdseg_label_resize_colorize_workspace_bytes ((OH + OW) ints; 0 for dims that are
+ * refused) or not 4-byte aligned. */
+#define MCDSEG_ENSEMBLE_MAX_K 16
+#define MCDSEG_ENSEMBLE_AVERAGING 0
+#define MCDSEG_ENSEMBLE_NMS 1
+int mcdseg_ensemble_probs(const float* const* maps, int32_t K, int32_t method, float* out, uint8_t* labels, int32_t n_used, int32_t N,
+                          int32_t C, int32_t H, int32_t W, void* stream);
+size_t mcdseg_label_resize_colorize_workspace_bytes(int32_t OH, int32_t OW);
+int mcdseg_label_resize_colorize(const uint8_t* labels, const uint8_t* palette, int32_t n_pal, uint8_t* label_out, uint8_t* vis_out,
+                                 int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2-byte activation storage (round 6): BASELINE config 5 ("drn_d_105 ... bf16 ... HBM-bound stress"; the network is the reference's
  * Bottleneck trunk, models/drn.py:62-100, 344-348, trained by adapt_trainer.py:155-220).  In the one-term arithmetic MCDSEG_MATH_F16X1

@@ -12,8 +12,8 @@ plus ``ave_ent_<x>.txt`` (mean entropy of pred_semseg1) and, when the data carry
 The decoder's heads run at 1/8 resolution; the x8 bilinear up-sampling is fused into the argmax / entropy kernel
 (``mcdseg_predict_labels_up8``) and into the depth-image kernel (``mcdseg_depth_image_u8``), so neither full-resolution tensor is
 stored.  pred_semseg2 is not evaluated: the reference computes it and drops it (its F2 average is commented out, :118-121), so
-``--use_f2`` only renames the output directory, as there.  The palette visualisation and ``eval.py`` run of the reference are
-outside this build.
+``--use_f2`` only renames the output directory, as there.  ``--vis`` adds ``vis/<name>``, the label PNG with a palette (``--palette_json``,
+or the PASCAL-VOC colours); the ``eval.py`` run of the reference is outside this build.
 
     python adapt_multitask_tester.py nyu train_output/...MCDmultitask/pth/MCD-normal-drn_d_38-40.pth.tar --synthetic
 """
@@ -54,6 +54,7 @@ def main(argv=None):
     mkdir_if_not_exist(label_outdir)
     mkdir_if_not_exist(depth_outdir)
     total_ent, images = 0.0, 0
+    save_vis = tester_common.vis_saver(args, t.base_outdir, t.n_used)
     with torch.no_grad():
         for imgs, gts, paths in t.loader:
             imgs = imgs.to(t.dev, non_blocking=True)
@@ -71,6 +72,8 @@ def main(argv=None):
             for k, path in enumerate(paths):
                 name = os.path.basename(path)
                 Image.fromarray(lab[k]).save(os.path.join(label_outdir, name))
+                if save_vis is not None:
+                    save_vis(lab[k], name)
                 Image.fromarray(depth[k]).save(os.path.join(depth_outdir, name))
     return label_outdir, depth_outdir, tester_common.finish(t.base_outdir, total_ent, images, t.meter)
 

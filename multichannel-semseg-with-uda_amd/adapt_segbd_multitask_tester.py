@@ -16,8 +16,8 @@ encloses (``--boundary_thre``, ``--min_thre``, ``--max_thre``) set to its majori
 
 The segmentation heads run at 1/8 resolution; the x8 bilinear up-sampling is fused into the argmax / entropy kernel
 (``mcdseg_predict_labels_up8``); the boundary map is one pass of ``mcdseg_boundary_head_fwd``.  pred_semseg2 is not evaluated: the reference computes it and drops it (its F2 average is commented out, :122-125), so
-``--use_f2`` only renames the output directory, as there.  The palette visualisation (``vis/``) and ``eval.py`` run of the reference are
-outside this build, as in the other testers.
+``--use_f2`` only renames the output directory, as there.  ``--vis`` adds ``vis/<name>``, the label PNG with a palette (``--palette_json``,
+or the PASCAL-VOC colours); the ``eval.py`` run of the reference is outside this build, as in the other testers.
 
     python adapt_segbd_multitask_tester.py nyu train_output/...MCD_segbd_multitask/pth/MCD-normal-drn_d_38-40.pth.tar --synthetic
 """
@@ -79,6 +79,7 @@ def main(argv=None):
     refiner = boundary_refine.BoundaryRefiner(t.base_outdir, args.boundary_thre, args.min_thre, args.max_thre, train_args.n_class,
                                               t.dev) if refine else None
     total_ent, images = 0.0, 0
+    save_vis = tester_common.vis_saver(args, t.base_outdir, t.n_used)
     with torch.no_grad():
         for imgs, gts, paths in t.loader:
             imgs = imgs.to(t.dev, non_blocking=True)
@@ -98,6 +99,8 @@ def main(argv=None):
             for k, path in enumerate(paths):
                 name = os.path.basename(path)
                 Image.fromarray(lab[k]).save(os.path.join(label_outdir, name))
+                if save_vis is not None:
+                    save_vis(lab[k], name)
                 resized.append(Image.fromarray(boundary[k]).resize(t.test_img_shape, Image.BILINEAR))
                 resized[k].save(os.path.join(boundary_outdir, name))
             if refiner is not None:  # on the bytes the boundary/ PNGs hold

@@ -4,8 +4,8 @@
 test shape), report the mean prediction entropy.
 
 On the HIP path eval-mode BatchNorm is folded into the convolution epilogue (``mcdseg_conv_fprop_affine``) and the
-argmax / entropy tail is one kernel (``mcdseg_predict_labels``).  The palette visualisation and ``eval.py`` of the
-reference are outside this build.
+argmax / entropy tail is one kernel (``mcdseg_predict_labels``).  ``--vis`` adds ``vis/<name>``, the label PNG with a palette
+(``--palette_json``, or the PASCAL-VOC colours); the ``eval.py`` run of the reference is outside this build.
 
     python adapt_tester.py nyu train_output/.../pth/MCD-normal-drn_d_38-1.pth.tar --synthetic
 """
@@ -47,6 +47,7 @@ def main(argv=None, mfnet=False):
     label_outdir = os.path.join(t.base_outdir, "label")
     mkdir_if_not_exist(label_outdir)
     total_ent, batches = 0.0, 0
+    save_vis = tester_common.vis_saver(args, t.base_outdir, t.n_used)
     with torch.no_grad():
         for imgs, gts, paths in t.loader:
             imgs = imgs.to(t.dev, non_blocking=True)
@@ -67,6 +68,8 @@ def main(argv=None, mfnet=False):
             for k, path in enumerate(paths):
                 img = Image.fromarray(lab[k]).resize(t.test_img_shape, Image.NEAREST)
                 img.save(os.path.join(label_outdir, os.path.basename(path)))
+                if save_vis is not None:
+                    save_vis(img, os.path.basename(path))
     return label_outdir, tester_common.finish(t.base_outdir, total_ent, batches, t.meter)
 
 

@@ -134,4 +134,7 @@ def get_da_mcd_testing_parser():
     g.add_argument("--synthetic_len", type=int, default=4)
     g.add_argument("--seed", type=int, default=4321)
     g.add_argument("-b", "--batch_size", type=int, default=1)
+    g.add_argument("--vis", action="store_true", help="also write vis/<name>: the label PNG with a palette (mode P)")
+    g.add_argument("--palette_json", type=str, default=None,
+                   help='with --vis: a {"palette": [[r,g,b],...]} file (default: the PASCAL-VOC colours of the classes used + 1)')
     return parser

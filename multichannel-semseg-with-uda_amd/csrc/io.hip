@@ -17,6 +17,7 @@
 // with 64-bit integer atomics, so the result does not depend on the order of execution.
 #include <cmath>
 #include "common.h"
+#include "nearest_index.h"
 
 namespace {
 
@@ -109,20 +110,7 @@ __global__ __launch_bounds__(256) void resize_pass_u8_kernel(const uint8_t* __re
   }
 }
 
-// ImagingScaleAffine (Geometry.c) source indices for NEAREST over a whole axis: xo = a0/2, then xo += a0 per step (sequential,
-// as Pillow accumulates it), index = xo < 0 ? -1 : (int)xo
-__global__ void nearest_index_kernel(int in_size, int out_size, int* __restrict__ idx) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const double a0 = (double)in_size / (double)out_size;
-  double xo = a0 * 0.5;
-  for (int x = 0; x < out_size; ++x) {
-    int xin = xo < 0.0 ? -1 : (int)xo;
-    xin = xin < 0 ? 0 : (xin > in_size - 1 ? in_size - 1 : xin);
-    idx[x] = xin;
-    xo += a0;
-  }
-}
-
+// (the NEAREST source indices, nearest_index_kernel, live in nearest_index.h: csrc/ensemble.hip gathers through them too)
 __global__ __launch_bounds__(256) void resize_nearest_u8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
                                                                 const int* __restrict__ ix, const int* __restrict__ iy, int N, int H,
                                                                 int W, int OH, int OW) {

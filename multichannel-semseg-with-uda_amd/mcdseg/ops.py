@@ -3093,6 +3093,73 @@ def depth_to_hha(depth, camera, unit_m=None, return_parts=False):
     return (out, parts) if return_parts else out
 
 
+# ------------------------------------------------------------------------------------------------ ensembling saved predictions
+ENSEMBLE_METHODS = {"averaging": 0, "nms": 1}  # MCDSEG_ENSEMBLE_AVERAGING / _NMS
+ENSEMBLE_MAX_K = 16                            # MCDSEG_ENSEMBLE_MAX_K
+
+
+def ensemble_probs(maps, method="averaging", n_used=None, want_prob=True):
+    """tools/ensemble_predict_from_npy.py:21-32 on the device: ``maps`` is a list of 2..16 fp32 GPU tensors of one
+    shape, [C,H,W] or [N,C,H,W] -- the saved maps of one image, or of a batch, one tensor per ensemble member, used where they lie ->
+    (``sum(maps) / len(maps)`` for "averaging" or ``np.max(maps, 0)`` for "nms", bit for bit as numpy evaluates them but for a NaN's
+    payload -- every NaN leaves as 0x7FC00000, an input NaN handed through by "nms" included --, or None without ``want_prob``; labels uint8 [H,W] / [N,H,W] = numpy's argmax over the first ``n_used`` classes, all by
+    default)."""
+    if isinstance(maps, torch.Tensor) or not isinstance(maps, (list, tuple)):
+        raise TypeError("mcdseg: ensemble_probs takes a list of tensors, one per ensemble member")
+    if not 2 <= len(maps) <= ENSEMBLE_MAX_K:
+        raise ValueError("mcdseg: ensemble_probs takes 2..%d maps, got %d" % (ENSEMBLE_MAX_K, len(maps)))
+    if method not in ENSEMBLE_METHODS:
+        raise ValueError("mcdseg: ensemble_probs method must be one of %s, got %r" % (sorted(ENSEMBLE_METHODS), method))
+    if any(torch.is_tensor(t) and t.requires_grad for t in maps):
+        raise RuntimeError("mcdseg: ensemble_probs is inference only: a map requires grad")
+    maps = [_req(t, "map %d" % k) for k, t in enumerate(maps)]
+    shape = tuple(maps[0].shape)
+    if len(shape) not in (3, 4) or maps[0].numel() == 0:
+        raise TypeError("mcdseg: ensemble_probs takes non-empty fp32 maps [C,H,W] or [N,C,H,W], got %s" % (shape,))
+    for k, t in enumerate(maps):
+        if tuple(t.shape) != shape or t.device != maps[0].device:
+            raise ValueError("mcdseg: ensemble_probs: map %d is %s on %s, map 0 is %s on %s" % (k, tuple(t.shape), t.device, shape, maps[0].device))
+    n, c, h, w = shape if len(shape) == 4 else (1,) + shape
+    n_used = c if n_used is None else int(n_used)
+    if not 1 <= n_used <= min(c, 256):
+        raise ValueError("mcdseg: ensemble_probs: n_used = %d outside [1, min(C = %d, 256)]" % (n_used, c))
+    dev = maps[0].device
+    out = torch.empty(shape, dtype=torch.float32, device=dev) if want_prob else None
+    labels = torch.empty(shape[:-3] + (h, w), dtype=torch.uint8, device=dev)
+    host = (ctypes.c_void_p * len(maps))(*[t.data_ptr() for t in maps])
+    with _timed("ensemble_probs", ((len(maps) + 1) * maps[0].numel(), 4 * maps[0].numel() * (len(maps) + bool(want_prob)) + labels.numel())):
+        check(lib().mcdseg_ensemble_probs(ctypes.cast(host, ctypes.c_void_p), len(maps), ENSEMBLE_METHODS[method], _p(out), _p(labels),
+                                          n_used, n, c, h, w, _stream()), "ensemble_probs")
+    _on_launch_stream(out, labels, *maps)
+    return out, labels
+
+
+def label_resize_colorize(labels_u8, out_wh, palette_u8, want_labels=True, want_vis=True):
+    """tools/ensemble_predict_from_npy.py:33-35 and :50-56 in one gather: uint8 label maps [N,H,W] -> (``Image.resize(out_wh, NEAREST)``
+    of each, uint8 [N,OH,OW]; the palette image of that, uint8 [N,OH,OW,3]); ``out_wh`` = (W, H) as the reference passes it, ``palette_u8``
+    a uint8 [n_pal,3] GPU tensor of 1..256 colours: a label >= n_pal is black.  An output that is not wanted is None."""
+    L = lib()
+    lab = _req_maps(labels_u8, "label batch", torch.uint8)
+    if not (want_labels or want_vis):
+        raise ValueError("mcdseg: label_resize_colorize: no output wanted")
+    pal = _req(palette_u8, "palette", torch.uint8)
+    if want_vis and (pal is None or pal.dim() != 2 or pal.shape[1] != 3 or not 1 <= pal.shape[0] <= 256):
+        raise TypeError("mcdseg: label_resize_colorize takes a uint8 palette [n_pal,3] of 1..256 colours")
+    ow, oh = int(out_wh[0]), int(out_wh[1])
+    if ow <= 0 or oh <= 0:
+        raise ValueError("mcdseg: label_resize_colorize: out_wh must be positive, got %s" % ((ow, oh),))
+    n, h, w = lab.shape
+    nbytes = L.mcdseg_label_resize_colorize_workspace_bytes(oh, ow)
+    ws = _ws(nbytes, lab.device)
+    out = torch.empty((n, oh, ow), dtype=torch.uint8, device=lab.device) if want_labels else None
+    vis = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=lab.device) if want_vis else None
+    with _timed("label_resize_colorize", (0, n * oh * ow * (1 + bool(want_labels) + 3 * bool(want_vis)))):
+        check(L.mcdseg_label_resize_colorize(_p(lab), _p(pal) if want_vis else None, pal.shape[0] if want_vis else 0, _p(out), _p(vis), n, h, w,
+                                             oh, ow, _p(ws), ctypes.c_size_t(nbytes), _stream()), "label_resize_colorize")
+    _on_launch_stream(lab, pal, ws, out, vis)
+    return out, vis
+
+
 def confusion_hist_(hist, gt, pred):
     """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated.  An entry
     whose prediction lies outside [0, n) is dropped too: it is not binned into a neighbouring row, as the reference's

@@ -4,13 +4,14 @@
 
     label/<name>       argmax over the non-background classes, resized NEAREST to the test shape
     prob/<name>.npy    the full-resolution logits (only with ---saves_prob)
+    vis/<name>         the label PNG with a palette, mode P (only with --vis)
 
 plus ``ave_ent_<x>.txt``, an empty ``data_list.txt`` (as the reference leaves it) and, when the data carry ground truth,
 ``eval_result.json``.  For ``suncg`` the outputs go one directory deeper, into the image's own subdirectory, as there.
 
 The model's last layer, the learned x8 up-sampler, is fused into the argmax / entropy kernel (``mcdseg_predict_labels_up8``): the
-full-resolution logits are formed only with ---saves_prob.  The palette visualisation and ``eval.py`` run of the reference are
-outside this build.
+full-resolution logits are formed only with ---saves_prob.  ``--vis`` adds ``vis/<name>``, the label PNG with a palette (``--palette_json``,
+or the PASCAL-VOC colours); the ``eval.py`` run of the reference is outside this build.
 
     python source_tester.py nyu train_output/suncg-train_only_6ch/pth/normal-drn_d_38-40.pth.tar --synthetic
 """
@@ -45,6 +46,9 @@ def get_parser():
     g.add_argument("--synthetic_len", type=int, default=4)
     g.add_argument("--seed", type=int, default=4321)
     g.add_argument("-b", "--batch_size", type=int, default=1)
+    g.add_argument("--vis", action="store_true", help="also write vis/<name>: the label PNG with a palette (mode P)")
+    g.add_argument("--palette_json", type=str, default=None,
+                   help='with --vis: a {"palette": [[r,g,b],...]} file (default: the PASCAL-VOC colours of the classes used + 1)')
     return parser
 
 
@@ -87,6 +91,7 @@ def main(argv=None):
     mkdir_if_not_exist(label_root)
     total_ent, images = 0.0, 0
     meter = tester_common.new_meter(train_args, dev)
+    save_vis = tester_common.vis_saver(args, base_outdir, n_used)
     with torch.no_grad():
         for imgs, gts, paths in loader:
             imgs = imgs.to(dev, non_blocking=True)
@@ -106,6 +111,8 @@ def main(argv=None):
                 label_outdir = add_subdir_if_necessary(label_root, subdir, args.tgt_dataset)
                 mkdir_if_not_exist(label_outdir)
                 Image.fromarray(lab[k]).save(os.path.join(label_outdir, name))
+                if save_vis is not None:
+                    save_vis(lab[k], name, subdir if args.tgt_dataset == "suncg" else None)
             del full
     return label_root, tester_common.finish(base_outdir, total_ent, images, meter)
 

@@ -8,6 +8,7 @@ and write per image
     aleatoric_uncertainty/<name>.png    sum over the classes of relu(up_std(scores)), resized (bilinear) to the test shape, then
                                         matplotlib's ``jet`` over the resized map's own range (what ``plt.imshow(.., cmap="jet")`` normalises to)
     aleatoric_uncertainty/<name>.npy    that map at full resolution, fp32 (only with ---saves_prob)
+    vis/<name>                          the label PNG with a palette, mode P (only with --vis; ``--palette_json``, or the PASCAL-VOC colours)
 
 plus ``ave_ent_<x>.txt`` and, when the data carry ground truth, ``eval_result.json``.  The reference's literal
 ``plt.imshow(std[0])`` (:162-166) takes the [C,H,W] array only for C = 3 or 4; the channel sum is what its own commented-out lines
@@ -83,6 +84,7 @@ def main(argv=None):
     mkdir_if_not_exist(uncertainty_root)
     total_ent, images = 0.0, 0
     meter = tester_common.new_meter(train_args, dev)
+    save_vis = tester_common.vis_saver(args, base_outdir, n_used)
     with torch.no_grad():
         for imgs, gts, paths in loader:
             imgs = imgs.to(dev, non_blocking=True)
@@ -98,6 +100,8 @@ def main(argv=None):
             for k, path in enumerate(paths):
                 name = os.path.basename(path)
                 Image.fromarray(lab[k]).save(os.path.join(label_root, name))
+                if save_vis is not None:
+                    save_vis(lab[k], name)
                 resized = np.asarray(Image.fromarray(std[k], mode="F").resize(test_img_shape, Image.BILINEAR))  # the scalar map first,
                 colour = Image.fromarray(jet_u8(resized))                                                       # then its colours
                 colour.save(os.path.join(uncertainty_root, os.path.splitext(name)[0] + ".png"))

@@ -9,7 +9,7 @@ import torch
 
 from datasets import get_dataset
 from eval import ConfusionMeter
-from util import check_if_done, load_checkpoint, mkdir_if_not_exist, save_dic_to_json
+from util import check_if_done, load_checkpoint, mkdir_if_not_exist, save_colorized_lbl, save_dic_to_json
 
 
 def unwrap(m):
@@ -40,7 +40,10 @@ def write_params(args, base_outdir):
     mkdir_if_not_exist(base_outdir)
     json_fn = os.path.join(base_outdir, "param.json")
     check_if_done(json_fn)
-    save_dic_to_json(dict(vars(args)), json_fn, verbose=False)
+    params = dict(vars(args))
+    if not params.get("vis"):  # param.json of a run without --vis stays what it was
+        params.pop("vis", None), params.pop("palette_json", None)
+    save_dic_to_json(params, json_fn, verbose=False)
 
 
 def make_loader(args, train_args, train_img_shape):
@@ -85,6 +88,26 @@ def save_probs(base_outdir, paths, full):
     mkdir_if_not_exist(prob_outdir)
     for k, path in enumerate(paths):
         np.save(os.path.join(prob_outdir, os.path.basename(path).replace("png", "npy")), full[k].cpu().numpy())
+
+
+def vis_saver(args, base_outdir, n_used):
+    """``--vis``: ``save(label, name, subdir=None)`` writes ``vis/[<subdir>/]<name>`` beside ``label/``: the label image (a uint8 array, or
+    the PIL image that went into ``label/``) in mode "P" with the colours of ``--palette_json``, or with the PASCAL-VOC colours of
+    ``n_used + 1`` labels (``ensemble.default_palette``).  None without the flag: no directory is made, nothing is written."""
+    if not getattr(args, "vis", False):
+        return None
+    from PIL import Image
+    import ensemble
+    palette = ensemble.load_palette(args.palette_json) if getattr(args, "palette_json", None) else ensemble.default_palette(min(n_used + 1, 256))
+    vis_root = os.path.join(base_outdir, "vis")
+    mkdir_if_not_exist(vis_root)
+
+    def save(label, name, subdir=None):
+        outdir = vis_root if subdir is None else os.path.join(vis_root, subdir)
+        mkdir_if_not_exist(outdir)
+        img = label.copy() if isinstance(label, Image.Image) else Image.fromarray(label)  # (putpalette changes the image it is given)
+        save_colorized_lbl(img, os.path.join(outdir, name), palette)
+    return save
 
 
 def finish(base_outdir, total_ent, count, meter):

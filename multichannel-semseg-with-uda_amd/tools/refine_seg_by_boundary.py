@@ -8,7 +8,7 @@ the labelling and the vote on the MI355X (``ops.refine_labels_by_boundary``).
 
 writes ``refined_label/<name>`` next to SEGDIR for every file of SEGDIR (refine_seg_by_bwboundary.py:13-16) and, with ``--gt_dir``
 (label PNGs of the same names and size, background 255), ``eval_result_refined.json`` = {"before": ..., "after": ...} beside it.  The
-palette images (``refined_vis/``) are outside this build, as ``vis/`` is in the testers."""
+palette images (``refined_vis/``) are outside this build."""
 import argparse
 import os
 import sys

@@ -75,6 +75,19 @@ def save_dic_to_json(dic, fn, verbose=True):
     print("param file '%s' was saved!" % fn)
 
 
+def save_colorized_lbl(idxed_lbl, outfn, palette):
+    """util.py:114-140: the 8-bit label image gets ``palette`` (uint8 [n,3]; the reference reads it from its dataset's info JSON) and is
+    saved as an indexed PNG (``putpalette`` turns mode "L" into "P": the indices stay the labels).  The palette is filled up to 256
+    entries with black: Pillow sizes a PNG's pixels by the palette's length (4 bits for up to 16 colours), which would cut a label
+    beyond a short palette down to its low bits instead of showing it black."""
+    import numpy as np
+    full = np.zeros((256, 3), dtype=np.uint8)
+    palette = np.asarray(palette, dtype=np.uint8).reshape(-1, 3)
+    full[:len(palette)] = palette
+    idxed_lbl.putpalette(full.flatten().tolist())
+    idxed_lbl.save(outfn)
+
+
 def emphasize_str(string):
     print("#" * 100)
     print(string)
