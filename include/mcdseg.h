@@ -789,6 +789,36 @@ int mcdseg_label_resize_colorize(const uint8_t* labels, const uint8_t* palette, 
                                  int32_t N, int32_t H, int32_t W, int32_t OH, int32_t OW, void* workspace, size_t workspace_bytes,
                                  void* stream);
 
+/* Edge maps of RGB images (tools/edge_detect.py:33-53 of the reference: the luma plane, cv2.Laplacian + 128, the Sobel magnitude and
+ * cv2.Canny; sample_scripts/refine_seg_by_boundary.sh:6 takes BOUNDARY_DIR = .../edges/canny from it) on the device (csrc/edge.hip;
+ * DESIGN.md section 4.15).  The definition is OpenCV's published 8-bit algorithm, all integer: no OpenCV build was at hand, so byte
+ * equality with a particular OpenCV build is neither claimed nor tested -- tests/edge_ref.py is the yardstick, bit for bit.
+ *
+ * mcdseg_edge_maps: ONE launch for whatever is asked.
+ *   rgb        uint8 [N][H][W][3], R, G, B;
+ *   luma       uint8 [N][H][W] = Y = (4899 R + 9617 G + 1868 B + 8192) >> 14 (cvtColor(BGR2YUV)[:,:,0]); written only when given;
+ *   laplacian  clip(Y[y-1][x] + Y[y+1][x] + Y[y][x-1] + Y[y][x+1] - 4 Y[y][x] + 128, 0, 255), BORDER_REFLECT_101 (-1 -> 1, L -> L - 2, a
+ *              dimension of length 1 -> 0);
+ *   sobel      min(floor(sqrt(dx^2 + dy^2)), 255), dx = the correlation with [[-1,0,1],[-2,0,2],[-1,0,1]], dy with its transpose,
+ *              BORDER_REFLECT_101;
+ *   canny_cls  0 / 1 (weak) / 2 (strong): dx, dy as above but BORDER_REPLICATE, mag = |dx| + |dy|, 0 outside the image; low > high are
+ *              swapped; mag <= low is 0; else with x = |dx|, y = |dy| << 15, t22 = 13573 x, t67 = t22 + (x << 16): y < t22 keeps
+ *              mag > left && mag >= right; y > t67 keeps mag > upper && mag >= lower; else, s = (dx ^ dy) < 0 ? -1 : 1, keeps
+ *              mag > mag[y-1][x-s] && mag > mag[y+1][x+s]; a kept pixel is 2 if mag > high, else 1;
+ *   each output may be NULL (not wanted), not all four; low and high are read only with canny_cls.
+ * -EINVAL before anything is launched: a null rgb; no output; a dimension < 1; N*H*W >= 2^31; N > 65535; more than 65535 tile rows.
+ *
+ * mcdseg_canny_hysteresis: edges uint8 [N][H][W] = 255 where cls is 1 or 2 and the pixel's 8-connected component of such pixels holds a
+ * 2, else 0 (any other value of cls reads as 0).  Connected components by the union-find of mcdseg_boundary_regions; the same bits run
+ * to run.  workspace: mcdseg_canny_hysteresis_workspace_bytes = 4*N*H*W (0 for dims that are refused); what it held does not matter.
+ * -EINVAL before anything is launched: a null cls or edges; edges == cls; the dims above; a workspace that is null, not 4-byte
+ * aligned or too small. */
+int mcdseg_edge_maps(const uint8_t* rgb, uint8_t* luma, uint8_t* laplacian, uint8_t* sobel, uint8_t* canny_cls, int32_t low,
+                     int32_t high, int32_t N, int32_t H, int32_t W, void* stream);
+size_t mcdseg_canny_hysteresis_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int mcdseg_canny_hysteresis(const uint8_t* cls, uint8_t* edges, int32_t N, int32_t H, int32_t W, void* workspace,
+                            size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * 2-byte activation storage (round 6): BASELINE config 5 ("drn_d_105 ... bf16 ... HBM-bound stress"; the network is the reference's
  * Bottleneck trunk, models/drn.py:62-100, 344-348, trained by adapt_trainer.py:155-220).  In the one-term arithmetic MCDSEG_MATH_F16X1

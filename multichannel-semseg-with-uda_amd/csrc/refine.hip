@@ -33,57 +33,13 @@
 // on the order of execution.  The slot NUMBERS do (an atomic counter hands them out), the output does not.
 #include <limits.h>
 #include "common.h"
+#include "union_find.h"
 
 namespace {
 
 constexpr int RF_TILE = 32;                       // tile edge of the LDS pass
 constexpr int RF_TILE_PIX = RF_TILE * RF_TILE;
 constexpr int RF_BINS = 256;                      // one per uint8 label value
-
-__device__ __forceinline__ int rf_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void rf_store(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ int rf_min(int* p, int v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// labels only ever decrease and label[x] <= x, so the chase ends at a root whoever writes meanwhile
-__device__ __forceinline__ int rf_find(int* label, int x) {
-  for (;;) {
-    const int p = rf_load(label + x);
-    if (p == x) return x;
-    x = p;
-  }
-}
-
-__device__ __forceinline__ void rf_union(int* label, int a, int b) {
-  for (;;) {
-    a = rf_find(label, a);
-    b = rf_find(label, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = rf_min(label + a, b);  // a was a root when read: link it below b
-    if (old == a) return;
-    a = old;  // somebody linked a first: its component (now below `old`) and b's still have to meet
-  }
-}
-
-__device__ __forceinline__ int rf_find_lds(int* label, int x) {
-  for (;;) {
-    const int p = __hip_atomic_load(label + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (p == x) return x;
-    x = p;
-  }
-}
-
-__device__ __forceinline__ void rf_union_lds(int* label, int a, int b) {
-  for (;;) {
-    a = rf_find_lds(label, a);
-    b = rf_find_lds(label, b);
-    if (a == b) return;
-    if (a < b) { const int t = a; a = b; b = t; }
-    const int old = __hip_atomic_fetch_min(label + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    if (old == a) return;
-    a = old;
-  }
-}
 
 __global__ __launch_bounds__(256) void refine_tile_kernel(const uint8_t* __restrict__ boundary, int thre, int* __restrict__ regions, int H,
                                                           int W) {

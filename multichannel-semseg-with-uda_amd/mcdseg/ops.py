@@ -3160,6 +3160,59 @@ def label_resize_colorize(labels_u8, out_wh, palette_u8, want_labels=True, want_
     return out, vis
 
 
+# ------------------------------------------------------------------------------------------------ edge maps of RGB images
+EDGE_KINDS = ("luma", "laplacian", "sobel", "canny_cls", "canny")
+
+
+def canny_hysteresis(cls_u8):
+    """Canny's hysteresis: a uint8 class map [N,H,W] (1 = weak, 2 = strong, anything else 0) -> uint8 [N,H,W],
+    255 where a weak or strong pixel's 8-connected component of such pixels holds a strong one, else 0"""
+    L = lib()
+    c = _req_maps(cls_u8, "class map", torch.uint8)
+    n, h, w = c.shape
+    nbytes = L.mcdseg_canny_hysteresis_workspace_bytes(n, h, w)
+    ws = _ws(nbytes, c.device)
+    edges = torch.empty_like(c)
+    with _timed("canny_hysteresis", (0, 14 * c.numel())):
+        check(L.mcdseg_canny_hysteresis(_p(c), _p(edges), n, h, w, _p(ws), ctypes.c_size_t(nbytes), _stream()), "canny_hysteresis")
+    _on_launch_stream(c, ws, edges)
+    return edges
+
+
+def edge_maps(rgb_u8, low=100, high=200, want=("laplacian", "sobel", "canny")):
+    """tools/edge_detect.py:33-53 of the reference on the device (OpenCV's published 8-bit algorithm, all integer):
+    uint8 RGB images [N,H,W,3] -> {key: uint8 [N,H,W]} for the keys of ``want`` out of "luma" (cvtColor's Y), "laplacian"
+    (cv2.Laplacian + 128, clipped), "sobel" (the clipped gradient magnitude), "canny_cls" (0 / weak 1 / strong 2 after the non-maximum
+    suppression at the thresholds ``low`` and ``high``) and "canny" (cv2.Canny: 0 / 255 after the hysteresis).  One launch forms
+    everything but "canny", whose hysteresis follows on a class map that is not returned unless "canny_cls" is asked for too."""
+    if isinstance(want, str):
+        want = (want,)
+    want = tuple(want)
+    unknown = [k for k in want if k not in EDGE_KINDS]
+    if unknown or not want:
+        raise ValueError("mcdseg: edge_maps: want must name some of %s, got %r" % (EDGE_KINDS, want))
+    if not torch.is_tensor(rgb_u8):
+        raise TypeError("mcdseg: edge_maps takes a uint8 [N,H,W,3] tensor")
+    if rgb_u8.dtype != torch.uint8:
+        raise TypeError("mcdseg: RGB batch must be torch.uint8, got %s" % rgb_u8.dtype)
+    if rgb_u8.dim() != 4 or rgb_u8.shape[3] != 3 or rgb_u8.numel() == 0:
+        raise ValueError("mcdseg: edge_maps takes non-empty RGB images [N,H,W,3], got %s" % (tuple(rgb_u8.shape),))
+    rgb = _req(rgb_u8, "RGB batch", torch.uint8)
+    n, h, w, _ = rgb.shape
+    new = lambda: torch.empty((n, h, w), dtype=torch.uint8, device=rgb.device)  # noqa: E731
+    out = {k: new() for k in ("luma", "laplacian", "sobel") if k in want}
+    cls = new() if ("canny" in want or "canny_cls" in want) else None
+    with _timed("edge_maps", (0, rgb.numel() + n * h * w * (len(out) + (cls is not None)))):
+        check(lib().mcdseg_edge_maps(_p(rgb), _p(out.get("luma")), _p(out.get("laplacian")), _p(out.get("sobel")), _p(cls), int(low),
+                                     int(high), n, h, w, _stream()), "edge_maps")
+    _on_launch_stream(rgb, cls, *out.values())
+    if "canny_cls" in want:
+        out["canny_cls"] = cls
+    if "canny" in want:
+        out["canny"] = canny_hysteresis(cls)
+    return {k: out[k] for k in EDGE_KINDS if k in out}
+
+
 def confusion_hist_(hist, gt, pred):
     """hist[n*gt + pred] += 1 for 0 <= gt < n (eval.py:21-23 fast_hist); ``hist`` int64 [n,n] on the GPU, accumulated.  An entry
     whose prediction lies outside [0, n) is dropped too: it is not binned into a neighbouring row, as the reference's
