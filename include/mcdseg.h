@@ -748,6 +748,53 @@ size_t mcdseg_depth_to_hha_workspace_bytes(int32_t N, int32_t H, int32_t W);
 int mcdseg_depth_to_hha(const float* depth_cm, const float* camera, uint8_t* hha, float* normals3, float* gravity, float* height, int32_t N,
                         int32_t H, int32_t W, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Depth inpainting by colorization (Levin, Lischinski, Weiss, SIGGRAPH 2004, as the NYU Depth toolbox's fill_depth_colorization applies
+ * it: the step between a sensor's raw depth and the maps the published HHA images were made from) on the device (csrc/fill.hip).  The
+ * procedure of DESIGN.md section 4.16 is the definition and tests/fill_ref.py its fp64 statement; nothing is claimed about byte
+ * equality with the MATLAB toolbox.  Per image of H*W >= 2 pixels:
+ *   known where depth_cm is finite, > 0 and, with max_valid_cm > 0, < max_valid_cm; g = ((0.299 R + 0.587 G) + 0.114 B) / 255;
+ *   zmax = the largest known depth, z = depth / zmax; an image without a known pixel is MCDSEG_FILL_EMPTY: not solved, all zeros;
+ *   weights over the 3 x 3 neighbours q of p inside the image, in row-major order: mu and the population variance var of g over them
+ *   and p; sigma = max(0.6 var, min_q (g_q - g_p)^2 / ln 100, 2e-6); w_pq = exp(-(g_q - g_p)^2 / sigma) / their sum;
+ *   the system (1 + alpha k_p) x_p - sum_q w_pq x_q = alpha k_p z_p (k = 1 at known pixels, else 0): M x = b, D = diag(M);
+ *   BiCGSTAB right-preconditioned by D from x0 = b/D, r = rhat = b - M x0, rho = a = omega = 1, v = p = 0; per iteration
+ *   rho' = rhat.r, beta = (rho'/rho)(a/omega), p = r + beta (p - omega v), v = M(p/D), a = rho'/(rhat.v), s = r - a v, t = M(s/D),
+ *   omega = (t.s)/(t.t), x += a (p/D) + omega (s/D), r = s - omega t;  filled = (float)(x zmax).
+ * Three calls share one workspace of mcdseg_fill_depth_workspace_bytes (one record per image, the block partials, the known depth in
+ * fp32, the eight weight planes and x r rhat p v s t b in fp64: 132 bytes per pixel; each part padded to 256 bytes; 0 for dims that are
+ * refused); the solver's scalars stay in it, on the device, and no call synchronises:
+ *   mcdseg_fill_depth_setup    rgb uint8 [N,H,W,3]; depth_cm fp32 [N,H,W], 4-byte aligned; alpha > 0 (the toolbox's is 1);
+ *                              max_valid_cm 0 for none.  Writes every part of the workspace the later calls read.
+ *   mcdseg_fill_depth_iterate  enqueues n_iter iterations, then one check of the TRUE residual b - M x: an image whose residual 2-norm is
+ *                              <= rtol |b| becomes MCDSEG_FILL_CONVERGED.  Only MCDSEG_FILL_RUNNING images are touched: every workgroup of
+ *                              another image returns at once, so an image's result and its iteration count are the same bits alone or
+ *                              beside slower images.  A zero or non-finite rho', rhat.v or t.t makes the image MCDSEG_FILL_BREAKDOWN
+ *                              with x the iterate of the last completed iteration.  n_iter = 0 is the check alone (the one before the
+ *                              first iteration).  status_out: N records { int32 status; int32 iterations; double |b - M x| / |b| } in
+ *                              device memory, 8-byte aligned, written for every image by every call (the residual is that of the
+ *                              image's last check; 0 for an empty image).  Stopping at an iteration limit is the caller's business.
+ *   mcdseg_fill_depth_finish   filled fp32 [N,H,W] centimetres at every pixel; with keep_known a known pixel gets its depth_cm back bit
+ *                              for bit; x_f64 [N,H,W], weights_f64 [N,8,H,W] (0 for a neighbour outside the image) and zmax_f64 [N] may
+ *                              be NULL.
+ * fp64 arithmetic, no atomics, plain launches in stream order (no grid barrier, no cooperative launch), every sum in an order that
+ * depends on H and W alone: the same bits run to run.
+ * -EINVAL before anything is launched: a null rgb, depth, status_out, filled or workspace; a dimension < 1; N > 65535; H*W < 2 or
+ * > 2^24; alpha or rtol not positive and finite; max_valid_cm negative or NaN; n_iter outside [0, 65536]; a workspace smaller than
+ * mcdseg_fill_depth_workspace_bytes or not 16-byte aligned; depth or filled not 4-byte aligned, status_out or an fp64 output not 8-byte
+ * aligned. */
+#define MCDSEG_FILL_RUNNING 0
+#define MCDSEG_FILL_CONVERGED 1
+#define MCDSEG_FILL_EMPTY 2
+#define MCDSEG_FILL_NOT_CONVERGED 3 /* never written by the library: what a caller reports for an image still running at its limit */
+#define MCDSEG_FILL_BREAKDOWN 4
+size_t mcdseg_fill_depth_workspace_bytes(int32_t N, int32_t H, int32_t W);
+int mcdseg_fill_depth_setup(const uint8_t* rgb, const float* depth_cm, double alpha, double max_valid_cm, int32_t N, int32_t H, int32_t W,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int mcdseg_fill_depth_iterate(int32_t n_iter, double rtol, int32_t N, int32_t H, int32_t W, void* workspace, size_t workspace_bytes,
+                              void* status_out, void* stream);
+int mcdseg_fill_depth_finish(int32_t N, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, float* filled, double* x_f64,
+                             double* weights_f64, double* zmax_f64, int32_t keep_known, void* stream);
+
 /* Ensembling of saved predictions (tools/ensemble_predict_from_npy.py:17-56 ensemble_predict) on the device (csrc/ensemble.hip;
  * DESIGN.md section 4.14).  All of it is exact: fp32 additions in a stated order, one division, comparisons, integer gathers.
  *

@@ -13,8 +13,12 @@
 //                  seg2bd_dv_kernel (fp64)                                                                   (seg2bd.hip)
 //                  prob_nll_partial_kernel (fp64)                                                            (fusion.hip)
 //                  hha_gravity_partial_kernel (fp64, twelve sums)                                            (hha.hip)
+//                  fill_system_kernel, fill_pv_kernel, fill_st_kernel, fill_xr_kernel, fill_residual_kernel
+//                  (fp64, one or two dot products of the BiCGSTAB iteration each, through fill_block_sums)     (fill.hip)
 //                  and every finalizer, through partials_total (loss_finalize_kernel: the same steps written out;
-//                  hha_gravity_final_kernel: twelve columns, then the eigen-step in thread 0).
+//                  hha_gravity_final_kernel: twelve columns, then the eigen-step in thread 0; fill_start_final_kernel,
+//                  fill_alpha_final_kernel, fill_omega_final_kernel, fill_rho_final_kernel, fill_check_final_kernel: one or two
+//                  columns, then the solver's scalars and the image's status in thread 0).
 //   chain_total  left to right from zero, ((0 + r0) + r1) + ...; the zero stays: 0.f + -0.f is +0.f:
 //                  up8_softmax_ce_l1_kernel, up8_softmax_ce_dist_kernel                                      (loss_front.h)
 //                  up8_softmax_ce_l1_dma_kernel, up8_softmax_ce_dist_dma_kernel (the same steps written out) (loss_front.h)

@@ -202,10 +202,20 @@ class DeviceInputPipeline(object):
             off += p.shape[3]
         return out
 
-    def hha(self, depth, camera, unit_m=None):
+    def hha(self, depth, camera, unit_m=None, fill_rgb=None, **fill_kw):
         """the HHA part of a depth batch [N,H,W] (``ops.depth_to_hha``: DESIGN.md section 4.13), uint8 [N,H,W,3] on the device:
-        ``images(rgb_u8, pipeline.hha(depth, camera, unit_m))`` is the whole 6-channel input path"""
-        return self._ops.depth_to_hha(depth.to(self.device, non_blocking=True), camera, unit_m)
+        ``images(rgb_u8, pipeline.hha(depth, camera, unit_m))`` is the whole 6-channel input path.  With ``fill_rgb`` (the uint8 RGB
+        batch [N,H,W,3] of the same frames) the depth's holes are inpainted first (``ops.fill_depth``: section 4.16; ``fill_kw`` are its
+        solver arguments) and the filled centimetres are encoded, all on the device."""
+        depth = depth.to(self.device, non_blocking=True)
+        if fill_rgb is None:
+            if fill_kw:
+                raise TypeError("DeviceInputPipeline.hha: %s given without fill_rgb" % sorted(fill_kw))
+            return self._ops.depth_to_hha(depth, camera, unit_m)
+        if fill_kw.get("return_parts"):
+            raise TypeError("DeviceInputPipeline.hha returns the HHA part alone: call ops.fill_depth for the solver's parts")
+        filled = self._ops.fill_depth(fill_rgb.to(self.device, non_blocking=True), depth, unit_m, **fill_kw)
+        return self._ops.depth_to_hha(filled, camera)
 
     def labels(self, lbl_u8, params=None):
         lbl_u8 = lbl_u8.to(self.device, non_blocking=True)

@@ -172,6 +172,10 @@ _SIGNATURES = {
     "mcdseg_dense_crf": (c_int, [c_void_p] * 5 + [c_i32] * 6 + [c_void_p, c_size_t, c_void_p]),
     "mcdseg_depth_to_hha_workspace_bytes": (c_size_t, [c_i32] * 3),
     "mcdseg_depth_to_hha": (c_int, [c_void_p] * 6 + [c_i32] * 3 + [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_fill_depth_workspace_bytes": (c_size_t, [c_i32] * 3),
+    "mcdseg_fill_depth_setup": (c_int, [c_void_p, c_void_p, ctypes.c_double, ctypes.c_double] + [c_i32] * 3 + [c_void_p, c_size_t, c_void_p]),
+    "mcdseg_fill_depth_iterate": (c_int, [c_i32, ctypes.c_double] + [c_i32] * 3 + [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "mcdseg_fill_depth_finish": (c_int, [c_i32] * 3 + [c_void_p, c_size_t] + [c_void_p] * 4 + [c_i32, c_void_p]),
     "mcdseg_ensemble_probs": (c_int, [c_void_p, c_i32, c_i32, c_void_p, c_void_p] + [c_i32] * 5 + [c_void_p]),
     "mcdseg_label_resize_colorize_workspace_bytes": (c_size_t, [c_i32] * 2),
     "mcdseg_label_resize_colorize": (c_int, [c_void_p, c_void_p, c_i32, c_void_p, c_void_p] + [c_i32] * 5 + [c_void_p, c_size_t, c_void_p]),
@@ -211,7 +215,7 @@ def sources():
 # backward under two ranks per device.  The compiler forms these instructions on its own from scalar fp32 source code, so the
 # files below are compiled with the packed-fp32 feature off, and ``packed_f32_opsel_sites`` (tests/test_cabi_and_host.py)
 # disassembles the built library to prove that no such instruction is left in ANY kernel.
-NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip", "seg2bd.hip", "augment.hip", "uncertain.hip", "dann.hip", "join.hip", "unet.hip", "crf.hip", "hha.hip", "ensemble.hip", "edge.hip"}
+NO_PACKED_F32 = {"bn.hip", "loss.hip", "multitask.hip", "fusion.hip", "io.hip", "sgd.hip", "adam.hip", "up8.hip", "infer.hip", "boundary.hip", "seg2bd.hip", "augment.hip", "uncertain.hip", "dann.hip", "join.hip", "unet.hip", "crf.hip", "hha.hip", "ensemble.hip", "edge.hip", "fill.hip"}
 CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=hidden"]
 NO_PK_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]  # (the host pass ignores it with a warning)
 OBJ_DIR = os.path.join(CSRC, "build")

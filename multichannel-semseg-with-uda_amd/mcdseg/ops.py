@@ -3056,24 +3056,28 @@ def _hha_cameras(camera, n):
     return (ctypes.c_float * (4 * n))(*cam.tolist())
 
 
+def _depth_cm(depth, unit_m, who):
+    """the dense fp32 centimetre batch [N,H,W] of a depth batch: what ``depth_to_hha`` and ``fill_depth`` both read"""
+    if not torch.is_tensor(depth) or depth.dim() != 3 or depth.numel() == 0:
+        raise TypeError("mcdseg: %s takes a non-empty depth batch [N,H,W]" % who)
+    if depth.dtype not in (torch.uint16, torch.int32, torch.float32):
+        raise TypeError("mcdseg: %s takes uint16, int32 or fp32 depth, got %s" % (who, depth.dtype))
+    if not depth.is_cuda:
+        raise RuntimeError("mcdseg: the depth batch must live on the GPU -- the HIP kernels are the only implementation (no CPU fallback)")
+    if unit_m is None:
+        if depth.dtype != torch.float32:
+            raise TypeError("mcdseg: %s needs unit_m (metres per unit) for %s depth" % (who, depth.dtype))
+        return _req(depth, "depth batch")
+    return _req(depth.float() * (100 * float(unit_m)), "depth batch")  # (a permuted batch keeps its strides through the multiply)
+
+
 def depth_to_hha(depth, camera, unit_m=None, return_parts=False):
     """Depth -> HHA: ``depth`` [N,H,W] on the GPU, fp32 in centimetres (``unit_m`` None) or uint16 / int32 / fp32
     in units of ``unit_m`` metres (0.001 for NYU and Kinect PNGs), converted by ONE fp32 multiply, ``depth.float() * (100 * unit_m)``;
     a value <= 0 or not finite is missing.  ``camera``: one (fx, fy, cx, cy) in pixels for the batch, or [N,4].  Returns the uint8 batch
     [N,H,W,3] (disparity, height, angle; (0,0,0) at a missing pixel) -- a part ``DeviceInputPipeline.images`` takes as it is -- and with
     ``return_parts`` also a dict of what it was rounded from: ``normals3`` fp32 [N,H,W,3], ``gravity`` fp32 [N,3], ``height`` fp32 [N,H,W]."""
-    if not torch.is_tensor(depth) or depth.dim() != 3 or depth.numel() == 0:
-        raise TypeError("mcdseg: depth_to_hha takes a non-empty depth batch [N,H,W]")
-    if depth.dtype not in (torch.uint16, torch.int32, torch.float32):
-        raise TypeError("mcdseg: depth_to_hha takes uint16, int32 or fp32 depth, got %s" % depth.dtype)
-    if not depth.is_cuda:
-        raise RuntimeError("mcdseg: the depth batch must live on the GPU -- the HIP kernels are the only implementation (no CPU fallback)")
-    if unit_m is None:
-        if depth.dtype != torch.float32:
-            raise TypeError("mcdseg: depth_to_hha needs unit_m (metres per unit) for %s depth" % depth.dtype)
-        z = _req(depth, "depth batch")
-    else:
-        z = _req(depth.float() * (100 * float(unit_m)), "depth batch")  # (a permuted batch keeps its strides through the multiply)
+    z = _depth_cm(depth, unit_m, "depth_to_hha")
     n, h, w = z.shape
     host = _hha_cameras(camera, n)
     L = lib()
@@ -3090,6 +3094,69 @@ def depth_to_hha(depth, camera, unit_m=None, return_parts=False):
                                     _p(parts and parts["gravity"]), _p(parts and parts["height"]), n, h, w, _p(ws),
                                     ctypes.c_size_t(nbytes), _stream()), "depth_to_hha")
     _on_launch_stream(z, ws, out, *(parts.values() if parts else ()))
+    return (out, parts) if return_parts else out
+
+
+# ------------------------------------------------------------------------------------------------ depth inpainting
+FILL_RUNNING, FILL_CONVERGED, FILL_EMPTY, FILL_NOT_CONVERGED, FILL_BREAKDOWN = 0, 1, 2, 3, 4  # MCDSEG_FILL_*
+FILL_STATUS_NAMES = {FILL_RUNNING: "running", FILL_CONVERGED: "converged", FILL_EMPTY: "empty", FILL_NOT_CONVERGED: "not_converged",
+                     FILL_BREAKDOWN: "breakdown"}
+
+
+def fill_depth(rgb_u8, depth, unit_m=None, alpha=1.0, rtol=1e-10, max_iter=4000, check_every=8, max_valid_cm=None, keep_known=False,
+               return_parts=False):
+    """Depth inpainting by colorization (the NYU toolbox's ``fill_depth_colorization`` step): ``rgb_u8`` uint8
+    [N,H,W,3] and ``depth`` [N,H,W] on the GPU, the depth as ``depth_to_hha`` takes it (fp32 centimetres, or uint16 / int32 / fp32 in
+    units of ``unit_m`` metres); a value <= 0, not finite or (with ``max_valid_cm``) >= max_valid_cm is missing.  Returns the filled
+    depth, fp32 centimetres [N,H,W], at EVERY pixel (``keep_known``: a known pixel keeps its measured value bit for bit).  The sparse
+    system of each image is solved by BiCGSTAB on the device, ``check_every`` iterations per call; the per-image status records are read
+    back after each call -- the only host synchronisation -- until no image is running or ``max_iter`` is reached.  Nothing raises on an
+    image that did not converge: with ``return_parts`` the second value is a dict of ``x`` fp64 [N,H,W] (the solution in units of
+    zmax), ``zmax`` fp64 [N], ``status`` int32 [N] (``FILL_CONVERGED``, ``FILL_EMPTY``: no known pixel, all zeros,
+    ``FILL_NOT_CONVERGED``, ``FILL_BREAKDOWN``), ``iterations`` int32 [N], ``residual`` fp64 [N] (the true residual's 2-norm over
+    |b| at the image's last check) -- these three on the CPU -- and ``weights`` fp64 [N,8,H,W]."""
+    z = _depth_cm(depth, unit_m, "fill_depth")
+    n, h, w = z.shape
+    if not torch.is_tensor(rgb_u8) or rgb_u8.dtype != torch.uint8 or tuple(rgb_u8.shape) != (n, h, w, 3):
+        raise TypeError("mcdseg: fill_depth takes a uint8 RGB batch %s beside the depth, got %s" %
+                        ((n, h, w, 3), (rgb_u8.dtype, tuple(rgb_u8.shape)) if torch.is_tensor(rgb_u8) else type(rgb_u8).__name__))
+    rgb = _req(rgb_u8, "RGB batch", torch.uint8)
+    alpha, rtol, max_iter, check_every = float(alpha), float(rtol), int(max_iter), int(check_every)
+    if not (0 < alpha < float("inf")) or not (0 < rtol < float("inf")):
+        raise ValueError("mcdseg: fill_depth: alpha and rtol must be positive and finite, got %r and %r" % (alpha, rtol))
+    if max_iter < 0 or check_every < 1:
+        raise ValueError("mcdseg: fill_depth: max_iter >= 0 and check_every >= 1 are needed, got %d and %d" % (max_iter, check_every))
+    if max_valid_cm is not None and not float(max_valid_cm) > 0:
+        raise ValueError("mcdseg: fill_depth: max_valid_cm must be positive (or None), got %r" % (max_valid_cm,))
+    if h * w < 2:
+        raise ValueError("mcdseg: fill_depth needs images of at least 2 pixels, got %d x %d" % (h, w))
+    L = lib()
+    nbytes = L.mcdseg_fill_depth_workspace_bytes(n, h, w)
+    ws = _ws64(nbytes, z.device)
+    records = torch.empty((n, 2), dtype=torch.float64, device=z.device)  # {int32 status; int32 iterations; double residual} each
+    dims, wsize = (n, h, w), ctypes.c_size_t(nbytes)
+    with _timed("fill_depth", (0, 132 * z.numel())):
+        check(L.mcdseg_fill_depth_setup(_p(rgb), _p(z), alpha, float(max_valid_cm or 0.0), *dims, _p(ws), wsize, _stream()), "fill_depth_setup")
+        done, step = 0, 0  # the first call is the check before the first iteration
+        while True:
+            check(L.mcdseg_fill_depth_iterate(step, rtol, *dims, _p(ws), wsize, _p(records), _stream()), "fill_depth_iterate")
+            done += step
+            host = records.cpu()
+            status, iterations = host.view(torch.int32)[:, 0].clone(), host.view(torch.int32)[:, 1].clone()
+            step = min(check_every, max_iter - done)
+            if step <= 0 or not bool((status == FILL_RUNNING).any()):
+                break
+        status[status == FILL_RUNNING] = FILL_NOT_CONVERGED
+        out = torch.empty((n, h, w), dtype=torch.float32, device=z.device)
+        parts = None
+        if return_parts:
+            parts = {"x": torch.empty((n, h, w), dtype=torch.float64, device=z.device),
+                     "zmax": torch.empty((n,), dtype=torch.float64, device=z.device),
+                     "status": status, "iterations": iterations, "residual": host[:, 1].clone(),
+                     "weights": torch.empty((n, 8, h, w), dtype=torch.float64, device=z.device)}
+        check(L.mcdseg_fill_depth_finish(*dims, _p(ws), wsize, _p(out), _p(parts and parts["x"]), _p(parts and parts["weights"]),
+                                         _p(parts and parts["zmax"]), int(bool(keep_known)), _stream()), "fill_depth_finish")
+    _on_launch_stream(z, rgb, ws, records, out, *((parts["x"], parts["zmax"], parts["weights"]) if parts else ()))
     return (out, parts) if return_parts else out
 
 
